@@ -3,7 +3,7 @@
 + SGD step, + RCCL gradient all-reduce when N > 1) of Model(SRyolo_MF.yaml) on synthetic
 1024x1024 RGB+IR batches, bf16 compute, batch 8 per GPU (BASELINE.json configs[1]/[2]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
@@ -83,6 +83,33 @@ def cpu_baseline(S=1024, iters=3):
                       f"(best {best_512:.3f}); torch threads={threads}, os.cpu_count()={n}"}
 
 
+DUMP_BUDGET = 64 << 20              # bytes written by --dump-outputs, all arrays together
+DUMP_SAMPLE = 1 << 22               # elements kept of an array too large for the budget
+
+
+def dump_outputs(out_dir, pred, loss, parts):
+    """Write what one training step returned as float32 .npy files: the head output pred[0] (B, na, ny, nx, nc + 5) and
+    the loss, plus (lbox, lobj, lcls) with the yolo loss.  An array over the budget is replaced by a fixed sample:
+    DUMP_SAMPLE flat indices from torch.randperm under seed 0, in ascending order (`<name>_sample.npy`); the indices
+    depend only on the array's size, so two builds run with the same arguments give comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    if len(parts) == 4:
+        arrays.update(lbox=parts[1].detach(), lobj=parts[2].detach(), lcls=parts[3].detach())
+    head = pred[0].detach()
+    small = sum(v.numel() * 4 for v in arrays.values())
+    if head.numel() * 4 + small <= DUMP_BUDGET:
+        arrays["pred0"] = head
+    else:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randperm(head.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+        arrays["pred0_sample"] = head.reshape(-1)[idx.to(head.device)]
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.float().cpu().numpy())
+    print(f"[bench] wrote {', '.join(sorted(arrays))} to {out_dir}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -94,7 +121,11 @@ def main():
     ap.add_argument("--loss", default="yolo", choices=["yolo", "mse"],
                     help="yolo: the reference's ComputeLoss (CIoU + BCE, device kernels) on fixed synthetic targets; mse: mean(pred^2)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (head output, loss) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # A timed number must come from the in-tree library running every store and every copy: refuse the diagnostic switches
     # (SODT_LIB_PATH swaps the whole .so for an A/B build; the retired SODT_HG_DBG / SODT_WMSA_ONE_WAVE used to ablate the
@@ -159,14 +190,16 @@ def main():
     def step():
         pred, _ = model(x_rgb, x_ir, "RGB+IR")
         if compute_loss is not None:
-            loss = compute_loss(pred, targets)[0] * world      # Train.py:418,440
+            parts = compute_loss(pred, targets)
+            loss = parts[0] * world      # Train.py:418,440
         else:
             loss = pred[0].float().square().mean()
+            parts = (loss,)
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
         ema.update(model)
-        return loss
+        return pred, loss, parts
 
     def barrier():
         if world > 1:
@@ -184,9 +217,13 @@ def main():
     evs = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in probe_idx] for _ in range(a.steps)]
     barrier()
     t0 = time.perf_counter()
+    last = None
     for k in range(a.steps):
         eng.probes_fwd = dict(zip(probe_idx, evs[k]))
-        step()
+        if k == a.steps - 1:
+            last = step()
+        else:
+            step()
     barrier()
     dt = time.perf_counter() - t0
     eng.probes_fwd = None
@@ -194,6 +231,9 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, *last)
+    last = None
 
     if rank == 0:
         t = S // 4

@@ -5,7 +5,7 @@ fixtures it writes.  The reference is imported on CPU with stub modules for the
 third-party packages that are absent (timm, cv2, torchvision, seaborn, numba) --
 the recipe recorded in SURVEY.md section 8(c).
 
-usage: python oracle/gen_golden.py [--skip-full]
+usage: python oracle/gen_golden.py [--skip-full | --only-{nms,loss,autocast,spp,spp-head,sr,pad,boundary}]
 """
 from __future__ import annotations
 
@@ -543,6 +543,73 @@ def pad_block_goldens(ref_vit, out):
     torch.save(g, os.path.join(out, "pad_block.pt"))
 
 
+def boundary_goldens(out):
+    """What the reference's own callers see of THIS package's Model (tests/test_boundary_contract.py): the hyperparameter
+    file (models/hyp.scratch.yaml), the state_dict layout of the reference Model(models/model.yaml) with a checksum of
+    every buffer, its Detect anchors / stride, the attributes and outputs of ComputeLoss (basics/utils/loss.py:90-163)
+    constructed on this Model, the anchors after check_anchor_order (basics/utils/autoanchor.py:13-21) and one
+    ModelEMA update (basics/utils/torch_utils.py:271-301) on hash-filled values.  Stored so that the test needs no
+    reference tree."""
+    import copy
+    import yaml
+    LM = importlib.import_module("reference.basics.utils.loss")
+    TU = importlib.import_module("reference.basics.utils.torch_utils")
+    AA = importlib.import_module("reference.basics.utils.autoanchor")
+    RM = importlib.import_module("reference.basics.models.model")
+    PM = importlib.import_module("small-object-detection-transformers_amd.model")
+    ref_dir = os.path.join("/root", "reference", "models")
+    hyp = yaml.safe_load(open(os.path.join(ref_dir, "hyp.scratch.yaml")))
+    g = dict(hyp=hyp)
+
+    rm = RM.Model(os.path.join(ref_dir, "model.yaml"), input_mode="RGB+IR", ch_steam=3, ch=128, nc=8)
+    pnames = {k for k, _ in rm.named_parameters()}
+    rsd = rm.state_dict()
+    g["state"] = [(k, tuple(v.shape), str(v.dtype).replace("torch.", ""), k in pnames) for k, v in rsd.items()]
+    g["buffer_sums"] = {k: (float(v.double().sum()), float(v.double().abs().sum())) for k, v in rsd.items() if k not in pnames}
+    rdet = rm.detect[-1]
+    g["detect"] = dict(anchors=rdet.anchors.clone(), anchor_grid=rdet.anchor_grid.clone(), stride=rdet.stride.clone(),
+                       na=rdet.na, nc=rdet.nc, nl=rdet.nl)
+
+    cfg = yaml.safe_load(open(os.path.join(ROOT, "small-object-detection-transformers_amd", "configs", "SRyolo_MF.yaml")))
+    torch.manual_seed(0)
+    m = PM.Model(cfg, input_mode="RGB+IR", ch_steam=3, ch=128, nc=8)
+    m.nc, m.hyp, m.gr = 8, hyp, 1.0
+    cl = LM.ComputeLoss(m)
+    torch.manual_seed(1)
+    pred = torch.randn(2, 3, 16, 16, 13, requires_grad=True)
+    tgt = torch.tensor([[0, 1, 0.5, 0.5, 0.2, 0.3], [1, 7, 0.25, 0.75, 0.1, 0.1], [1, 0, 0.6, 0.2, 0.3, 0.2]])
+    loss, lbox, lobj, lcls = cl([pred], tgt)
+    loss.backward()
+    mine = R.compute_loss(pred.detach(), tgt, m.detect[-1].anchors[0], hyp={k: hyp[k] for k in R.LOSS_HYP}, gr=1.0, nc=8)
+    print(f"[pin] boundary ComputeLoss: loss {float(loss):.5f} oracle diff {maxdiff(mine[0], loss):.2e}")
+    g["compute_loss"] = dict(na=cl.na, nc=cl.nc, nl=cl.nl, balance=list(cl.balance), anchors=cl.anchors.clone(),
+                             pred=pred.detach().clone(), targets=tgt, loss=loss.detach().clone(), lbox=lbox.detach().clone(),
+                             lobj=lobj.detach().clone(), lcls=lcls.detach().clone(), dpred=pred.grad.clone())
+
+    det = copy.deepcopy(m.detect[-1])
+    AA.check_anchor_order(det)
+    g["anchor_order"] = dict(anchors=det.anchors.clone(), anchor_grid=det.anchor_grid.clone())
+
+    # ModelEMA: the averaged entries are set to hash values A before the copy and to B on the model before update()
+    keys = ["image_encoder.stage1.0.norm1.weight", "image_encoder.stage1.0.attn.qkv.bias", "detect.4.bn.running_mean"]
+    msd = m.state_dict()
+    A = {k: R._hash01(f"emaA:{k}", msd[k].numel()).view(msd[k].shape).float() for k in keys}
+    B = {k: R._hash01(f"emaB:{k}", msd[k].numel()).view(msd[k].shape).float() for k in keys}
+    with torch.no_grad():
+        for k in keys:
+            msd[k].copy_(A[k])
+    ema = TU.ModelEMA(m)
+    with torch.no_grad():
+        for k in keys:
+            msd[k].copy_(B[k])
+    ema.update(m)
+    esd = ema.ema.state_dict()
+    g["ema"] = dict(keys=list(esd.keys()), averaged=[k for k, v in esd.items() if v.dtype.is_floating_point],
+                    decay=ema.decay(ema.updates), updates=ema.updates, A=A, B=B, result={k: esd[k].clone() for k in keys})
+    torch.save(g, os.path.join(out, "boundary.pt"))
+    print("[pin] wrote boundary.pt")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-full", action="store_true")
@@ -553,6 +620,7 @@ def main():
     ap.add_argument("--only-spp-head", action="store_true")
     ap.add_argument("--only-sr", action="store_true")
     ap.add_argument("--only-pad", action="store_true")
+    ap.add_argument("--only-boundary", action="store_true")
     a = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(os.cpu_count() or 8)
@@ -562,6 +630,9 @@ def main():
         return
     if a.only_pad:
         pad_block_goldens(ref_vit, GOLD)
+        return
+    if a.only_boundary:
+        boundary_goldens(GOLD)
         return
     if a.only_autocast:
         autocast_goldens(ref_model, GOLD)
@@ -583,6 +654,7 @@ def main():
     pad_block_goldens(ref_vit, GOLD)
     spp_goldens(ref_common, GOLD)
     sr_goldens(GOLD)
+    boundary_goldens(GOLD)
     if not a.skip_full:
         full_model_goldens(ref_model, GOLD)
         autocast_goldens(ref_model, GOLD)
