@@ -385,6 +385,37 @@ int sodt_nms_select(const float* z, int nc, const unsigned long long* keys, long
                     int agnostic, void* ws, size_t ws_bytes, float* out, int* out_index, int* out_count,
                     sodt_stream_t st);
 
+/* ---- validation statistics (basics/test.py:155-264, basics/utils/metrics.py:18-106), eval only ----------------
+ * sodt_eval_match: the per-image true-positive matching of test.py:155-240 for a whole batch at once.
+ *   det: the NMS rows of all images packed, (n_det, 6) f32 [x1 y1 x2 y2 conf cls] in letterboxed-input pixels;
+ *   det_off: (B+1) device int32 image offsets into det.  targets: (nt, 6) f32 [img cls x y w h] in input pixels
+ *   (test.py:149), in any order - grouped by image on the device, each image's rows kept in their order.
+ *   geom: (B, 5) f32 [h0 w0 gain padw padh] per image (scale_coords' img0_shape and ratio_pad, general.py:323-336).
+ *   iouv: the 10 IoU thresholds, a HOST array (torch.linspace(0.5, 0.95, 10), test.py:100).
+ *   correct: (n_det, 10) uint8, test.py:206-237 bit for bit (scale_coords of predictions and xywh2xyxy'd labels,
+ *   box_iou, max(1) with the lowest target index on ties, the greedy per-class walk in NMS row order, iou > iouv).
+ *   tcls_out: (nt) f32, the target classes in image order (test.py:159's tcls concatenated); rows whose image index is
+ *   not an integer in [0, B) match nothing and are written as -1.  Any number of labels per image.
+ *   ws: scratch of at least sodt_eval_match_workspace_bytes(B, n_det, nt).
+ * sodt_ap_per_class: ap_per_class + compute_ap (metrics.py:18-106) in f64.  tp (n, 10) uint8, conf / pred_cls (n) f32,
+ *   target_cls (nt) f32; classes are integral values in [0, nc), nc <= 4096.  Negative target classes are padding and
+ *   ignored; other target classes outside [0, nc) are counted in info[1] (the result is then not the reference's);
+ *   predictions of a class no target has are ignored, as in the reference.  Outputs, first info[0] = nc_u rows valid:
+ *   p, r, f1 (nc) f64 at the first argmax of f1.mean(0); ap (nc, 10) f64; classes (nc) int32 = np.unique(target_cls);
+ *   nt_count (nc) int32 = np.bincount(target_cls, minlength=nc) (test.py:261).  info: int32[4] =
+ *   [nc_u, bad target classes, rows of tp with any true entry, argmax index].  Predictions are ordered by descending
+ *   confidence with ties in row order (a stable sort; the reference's np.argsort(-conf) leaves ties unordered).
+ *   ws: scratch of at least sodt_ap_per_class_workspace_bytes(n, nt, nc).
+ * Neither entry allocates or synchronises. */
+int sodt_eval_match_workspace_bytes(int B, long n_det, long nt, size_t* bytes);
+int sodt_eval_match(const float* det, const int* det_off, int B, long n_det, const float* targets, long nt,
+                    const float* geom, const float* iouv, void* ws, size_t ws_bytes, unsigned char* correct,
+                    float* tcls_out, sodt_stream_t st);
+int sodt_ap_per_class_workspace_bytes(long n, long nt, int nc, size_t* bytes);
+int sodt_ap_per_class(const unsigned char* tp, const float* conf, const float* pred_cls, long n, const float* target_cls,
+                      long nt, int nc, void* ws, size_t ws_bytes, double* p, double* r, double* f1, double* ap,
+                      int* classes, int* nt_count, int* info, sodt_stream_t st);
+
 /* Batched parameter preparation: out = cast(permute3(in)) for a device-resident table. */
 typedef struct {
   const float* src; void* dst;

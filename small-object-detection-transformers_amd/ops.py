@@ -509,6 +509,37 @@ def nms_select(z_img, keys, n_total, iou_thres, agnostic, ws, out, out_index, ou
             int(bool(agnostic)), _p(ws), ws.numel() * ws.element_size(), _p(out), _p(out_index), _p(out_count))
 
 
+def eval_match_workspace_bytes(B: int, n_det: int, nt: int) -> int:
+    b = C.c_size_t(0)
+    rc = _lib.sodt_eval_match_workspace_bytes(int(B), int(n_det), int(nt), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_eval_match_workspace_bytes failed with status {rc}")
+    return int(b.value)
+
+
+def eval_match(det, det_off, targets, geom, iouv, ws, correct, tcls_out):
+    """Per-image true-positive matching of test.py:155-240 for one batch: det (n_det, 6) f32 packed NMS rows,
+    det_off (B+1) int32, targets (nt, 6) f32 pixel-space, geom (B, 5) f32, iouv: 10 host floats."""
+    B = det_off.numel() - 1
+    thr = (C.c_float * 10)(*[float(v) for v in iouv])
+    _launch("sodt_eval_match", _p(det), _p(det_off), B, det.shape[0], _p(targets), targets.shape[0], _p(geom), thr,
+            _p(ws), ws.numel() * ws.element_size(), _p(correct), _p(tcls_out))
+
+
+def ap_per_class_workspace_bytes(n: int, nt: int, nc: int) -> int:
+    b = C.c_size_t(0)
+    rc = _lib.sodt_ap_per_class_workspace_bytes(int(n), int(nt), int(nc), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_ap_per_class_workspace_bytes failed with status {rc} (nc must be in [1, 4096])")
+    return int(b.value)
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls, nc, ws, p, r, f1, ap, classes, nt_count, info):
+    """ap_per_class + compute_ap of metrics.py:18-106 on the device (f64 outputs, first info[0] rows valid)."""
+    _launch("sodt_ap_per_class", _p(tp), _p(conf), _p(pred_cls), tp.shape[0], _p(target_cls), target_cls.numel(), int(nc),
+            _p(ws), ws.numel() * ws.element_size(), _p(p), _p(r), _p(f1), _p(ap), _p(classes), _p(nt_count), _p(info))
+
+
 def prep_weights(table_dev, n, max_elems, dtype_code):
     _launch("sodt_prep_weights", _p(table_dev), n, max_elems, dtype_code)
 
