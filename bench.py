@@ -3,10 +3,15 @@
 + SGD step, + RCCL gradient all-reduce when N > 1) of Model(SRyolo_MF.yaml) on synthetic
 1024x1024 RGB+IR batches, bf16 compute, batch 8 per GPU (BASELINE.json configs[1]/[2]).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps, write the outputs when
+--dump-outputs is given, print the result line.  `roofline` comes with it: it is read off HIP events inside the timed
+steps and takes no run of its own.  --full adds the measurements that do take time of their own: today the CPU baseline
+(about 40 s of host work on a 16-core share).
+
+Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline     - the kernel BASELINE.json's north_star prices: the fused W-MSA / SW-MSA block kernel
                  (csrc/wmsa_hg.hip: LN1 + QKV + window attention + proj + residual + LN2 in one launch), the six
                  stage-1 launches of every step timed live with HIP events on the launch stream inside the timed
@@ -14,7 +19,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                  dense bf16.  `traffic` = HBM bytes per launch from the PMC passes in profiles/ (FETCH_SIZE x 2 +
                  WRITE_SIZE, MI355X_MICROARCH.md), printed only when that profile was taken with the SAME kernel source
                  (sha256 of csrc/wmsa_hg.hip recorded in the file), else null
-  cpu_baseline - the CPU oracle (oracle/ref_torch.py, a port) timed on this host's cores, rank 0 at N=1 only:
+  cpu_baseline - with --full only: the CPU oracle (oracle/ref_torch.py, a port) timed on this host's cores, rank 0 at N=1:
                  B=1 @1024^2 directly and B=2 @512^2, fwd+bwd, 3 timed iterations each after a warm-up; `value` is the
                  median at 1024^2, both medians and bests are in `sample`
 """
@@ -120,7 +125,9 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--loss", default="yolo", choices=["yolo", "mse"],
                     help="yolo: the reference's ComputeLoss (CIoU + BCE, device kernels) on fixed synthetic targets; mse: mean(pred^2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline, N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (head output, loss) as DIR/<name>.npy")
     a = ap.parse_args()
@@ -275,7 +282,7 @@ def main():
                          "hbm_achieved_GBps": round(alg_bytes / (kern_ms * 1e-3) / 1e9, 1),
                          "hbm_frac": round(alg_bytes / (kern_ms * 1e-3) / 1e9 / PEAK_HBM, 4), "traffic": traffic, "traffic_profile": prof},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S)
         print(json.dumps(out), flush=True)
     if world > 1:
