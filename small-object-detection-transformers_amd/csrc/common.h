@@ -97,7 +97,8 @@ template <> __device__ __forceinline__ uint4 pack<bf16>(const float* f) {
   return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
 }
 
-// erf(x/sqrt2) by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, far inside the 1e-3 logit gate) and the
+// erf(x/sqrt2) by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7 for the formula, <= 1.5e-7 + 2^-22 evaluated in f32 with the
+// hardware exp / rcp; far inside the 1e-3 logit gate) and the
 // Gaussian exp(-x^2/2) it shares with gelu'(x): ~14 VALU ops instead of libm erff's ~50.
 __device__ __forceinline__ void erf_gauss(float x, float& erfv, float& gauss) {
   const float ax = fabsf(x) * 0.70710678118654752f;
@@ -120,7 +121,9 @@ __device__ __forceinline__ float dgelu_f(float x) {
   return 0.5f * (1.0f + e) + x * 0.3989422804014327f * g;
 }
 // bf16 throughput path: erf(x / sqrt 2) as an odd degree-15 polynomial in the clamped argument (near-minimax fit of
-// erf(z)/z in z^2 on [0, 2.7]; |err| <= 4.2e-5 inside, 1.4e-4 on the clamped tail - far below bf16's 3.9e-3) - no
+// erf(z)/z in z^2 on [0, 2.7]; |err| <= 4.2e-5 inside, 1.8e-4 on the clamped tail = 1 - erf_poly(2.7 sqrt 2), the 1.34e-4 of the
+// clamp itself plus the fit's own error at its end point - far below bf16's 3.9e-3; an error on erf, so GELU = x/2 (1 + erf) carries
+// |x|/2 times it: 0.26 at x = -3000, where GELU is 0) - no
 // rcp / exp on the quarter-rate transcendental unit, and pure FMA chains that hipcc packs into v_pk_fma_f32.
 // The f32 parity path keeps the 1.5e-7 form above.
 __device__ __forceinline__ float erf_poly(float x) {

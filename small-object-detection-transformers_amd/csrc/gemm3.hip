@@ -436,9 +436,10 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(const sodt_gemm_args g) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               if (RC) v[j] *= x[j];                               // parked gelu'(h)
-              else if (CF & SODT_EPI_DGELU) v[j] *= dgelu_t<bf16>(x[j]);     // same order as epi_chunk: (bias, dgelu | drelu, resid)
+              else if (CF & SODT_EPI_DGELU) v[j] *= dgelu_t<bf16>(x[j]);     // (dgelu / drelu come without a bias here)
               else if (CF & SODT_EPI_DRELU) v[j] = x[j] > 0.f ? v[j] : 0.f;
-              else v[j] += x[j];
+              else v[j] += x[j];                                  // residual BEFORE the bias below (epi_chunk adds the bias
+                                                                  //  first): the f32 sums may differ in their last bit
             }
           }
           if ((CF & SODT_EPI_BIAS) && !RC) {
