@@ -129,7 +129,11 @@ int sodt_layernorm_bwd(const void* dy, const void* x, const float* stats, const 
  * (backbone_vit.py:968-989 + :1094-1124): cyclic shift, window partition, q*scale@k^T,
  * relative-position bias, -100 shift mask, softmax, @v, un-partition, un-shift are all
  * index arithmetic inside the kernel.  qkv [B*H*W][3C], out [B*H*W][C], lse f32
- * [B*H*W][heads], bias_t f32 [heads][(2ws-1)^2] (transposed table). */
+ * [B*H*W][heads], bias_t f32 [heads][(2ws-1)^2] (transposed table).  Accepted geometry:
+ * ws in {8, 16, 32, 64} dividing H and W, 0 <= shift < ws, head dim C/heads in {16, 32, 64},
+ * and heads divisible by the waves per workgroup of the (dtype, head dim) instantiation
+ * (forward: bf16 4/4/2, f32 4/2/2 for head dim 16/32/64; backward: bf16 4/2/1, f32 2/2/1).
+ * Anything else returns SODT_EINVAL without writing. */
 int sodt_window_attn_fwd(const void* qkv, const float* bias_t, void* out, float* lse,
                          int B, int H, int W, int C, int heads, int ws, int shift,
                          int dtype, sodt_stream_t st);
