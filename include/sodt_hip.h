@@ -443,6 +443,22 @@ int sodt_sgd_ema_step(float* p, const float* g, float* mom, float* ema, void* p_
                       const float* momentum, const float* weight_decay, int nesterov, float grad_scale,
                       float ema_decay, sodt_stream_t st);
 
+/* The Adam sibling of sodt_sgd_ema_step (csrc/optim.hip), same buffers, group map, EMA and cast tail, one launch: what the
+ * reference does with optim.Adam(pg0, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999)) under --adam (Train.py:147-148, :627)
+ * over the same weight-decay groups, or with the AdamW of basics/optimizer.py:11-33 (decoupled != 0), followed by
+ * ModelEMA.update and the cast.  torch.optim.Adam / AdamW semantics with amsgrad=False, maximize=False; step = t >= 1 is
+ * the number of this update (one counter: every owned parameter steps together).  lr / beta1 / beta2 / eps / weight_decay
+ * are host arrays of ngroups <= 4 DOUBLES: 1 - beta, lr / (1 - beta1^t), sqrt(1 - beta2^t) and 1 - lr*wd are formed from
+ * them in double, as torch forms them from Python floats, and only then rounded to the floats the kernel reads.
+ *   coupled: d = g*grad_scale + wd*p, p0 = p;   decoupled: d = g*grad_scale, p0 = p*(1 - lr*wd)
+ *   m = b1*m + (1-b1)*d;  v = b2*v + (1-b2)*d*d;  p = p0 - lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ *   ema, p_cast as in sodt_sgd_ema_step.  SODT_EINVAL: null / misaligned buffers, n_elems % 4, ngroups outside 1..4,
+ *   step < 1, eps <= 0, a beta outside [0, 1), an unknown cast_dtype. */
+int sodt_adam_ema_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* ema, void* p_cast, int cast_dtype,
+                       const unsigned char* group_of_chunk, long n_elems, int ngroups, const double* lr,
+                       const double* beta1, const double* beta2, const double* eps, const double* weight_decay,
+                       int decoupled, long step, float grad_scale, float ema_decay, sodt_stream_t st);
+
 /* Input pre-processing of the training / evaluation loop (csrc/preprocess.hip): `imgs.to(device).float() / 255.0` followed by
  * `F.interpolate(image, size=[i // down_factor ...], mode='bilinear', align_corners=True)` (Train.py:364-374; test.py:124-129
  * is the factor-1 case) for the RGB and the IR batch in one launch.  rgb / ir: uint8 (B, c, Hin, Win) contiguous (device);
@@ -462,6 +478,13 @@ int sodt_yolo_loss_workspace_bytes(long ncells, int nt, int nc, size_t* bytes);
 int sodt_yolo_loss(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx,
                    int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr,
                    void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st);
+/* The same with the reference's FocalLoss(BCEWithLogitsLoss(pos_weight), gamma=fl_gamma, alpha=0.25) around the class and
+ * the objectness BCE (basics/utils/loss.py:36-62, :103-108; hyp['fl_gamma'], mutated by --evolve, Train.py:720), value and
+ * gradient.  fl_gamma == 0 is sodt_yolo_loss, kernel for kernel; fl_gamma < 0 or NaN: SODT_EINVAL.  The gradient stays
+ * finite where 1 - p_t rounds to 0 (saturated logits, gamma < 1), where the reference's autograd gives inf * 0. */
+int sodt_yolo_loss_fl(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx,
+                      int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr,
+                      float fl_gamma, void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st);
 
 /* hipMemsetAsync(p, 0, bytes) on the stream (statistics / gradient accumulators) */
 int sodt_memset_zero(void* p, long bytes, sodt_stream_t st);

@@ -123,6 +123,9 @@ SIGNATURES = {
     "sodt_maxpool5_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_yolo_loss_workspace_bytes": [_L, _I, _I, C.POINTER(C.c_size_t)],
     "sodt_yolo_loss": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, C.c_size_t, _P, _P, _P],
+    "sodt_yolo_loss_fl": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, C.c_size_t, _P, _P, _P],
+    "sodt_adam_ema_step": [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _L, _F, _F, _P],
     "sodt_sgd_ema_step": [_P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                           _I, _F, _F, _P],
     "sodt_preprocess_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

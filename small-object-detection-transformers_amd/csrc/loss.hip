@@ -15,6 +15,17 @@
 //   scatter     box and class gradients of every valid candidate added (atomics: duplicates accumulate, as autograd's
 //               index backward does), scaled by 1/n known only now.
 //   finalize    (loss * batch, lbox, lobj, lcls) exactly as loss.py:157-163.
+// Focal loss (fl_gamma > 0, the reference's FocalLoss(BCEWithLogitsLoss(pos_weight), gamma, alpha=0.25) around both BCE
+// terms, basics/utils/loss.py:36-62, :103-108; what Train.py's --evolve mutates, :720) is the FOCAL = true instantiation of
+// the candidates and obj_dense kernels, same four launches:
+//   p = sigmoid(x)   p_t = t p + (1 - t)(1 - p)   a_t = 0.25 t + 0.75 (1 - t)   bce = pw t softplus(-x) + (1 - t) softplus(x)
+//   L = a_t (1 - p_t)^gamma bce
+//   dL/dx = a_t [ (1 - p_t)^gamma dbce/dx - gamma (1 - p_t)^(gamma - 1) (2 t - 1) p (1 - p) bce ]
+// for any target t in [0, 1] (the objectness target is the gr-blended IoU).  1 - p_t is formed without cancellation as
+// t sigmoid(-x) + (1 - t) sigmoid(x).  For saturated logits it can still round to exactly 0; with gamma < 1 the
+// reference's autograd then multiplies inf by 0.  Here the second term is dropped when 1 - p_t == 0: its limit is 0
+// because bce falls faster than (1 - p_t)^(gamma - 1) grows, so the gradient stays finite.  fl_gamma == 0 runs the
+// FOCAL = false instantiations, which are the kernels as they were before focal loss existed.
 // Latency-bound (a few hundred candidates), except obj_dense which streams pred / dpred once: 2 x B*na*ny*nx*no*4 bytes.
 #include "common.h"
 #include "../../include/sodt_hip.h"
@@ -29,6 +40,7 @@ struct LossArgs {
   int* winner; float* rec; double* sums;       // rec: [ncand][6 + nc]: cell, valid, iou, g0..g3, gcls[nc]; sums: box, cls, obj, n
   int B, na, ny, nx, nc, no, nt;
   float h_box, h_cls, cls_pw, h_obj, obj_pw, anchor_t, gr;
+  float fl_gamma;                                // read by the FOCAL instantiations only
 };
 
 struct D4 { float v, d[4]; };
@@ -49,7 +61,20 @@ __device__ __forceinline__ D4 clamp0(const D4& a) { return a.v > 0.f ? a : dc(0.
 __device__ __forceinline__ D4 datan(const D4& a) { D4 r; r.v = atanf(a.v); const float k = 1.0f / (1.0f + a.v * a.v); for (int i = 0; i < 4; ++i) r.d[i] = a.d[i] * k; return r; }
 __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+// FocalLoss.forward (loss.py:45-55) of one logit against target t in [0, 1]: value, and its derivative in *dx
+__device__ __forceinline__ float focal_bce(float x, float t, float pw, float gamma, float* dx) {
+  const float s = sigm(x), sn = sigm(-x);                              // p and 1 - p
+  const float bce = pw * t * softplus(-x) + (1.f - t) * softplus(x);
+  const float dbce = -pw * t * sn + (1.f - t) * s;
+  const float q = t * sn + (1.f - t) * s;                              // 1 - p_t
+  const float at = 0.25f * t + 0.75f * (1.f - t);
+  const float mod = powf(q, gamma);
+  const float dmod = q > 0.f ? gamma * (mod / q) * (1.f - 2.f * t) * s * sn : 0.f;
+  *dx = at * (mod * dbce + dmod * bce);
+  return at * mod * bce;
+}
 
+template <bool FOCAL>
 __global__ __launch_bounds__(128) void loss_candidates_kernel(const LossArgs a) {
   const int c = blockIdx.x * 128 + threadIdx.x;
   const int ncand = 5 * a.na * a.nt;
@@ -107,9 +132,16 @@ __global__ __launch_bounds__(128) void loss_candidates_kernel(const LossArgs a) 
   double cls_sum = 0.0;
   if (a.nc > 1) {
     for (int k = 0; k < a.nc; ++k) {                                   // BCEWithLogits(pos_weight) (:142-144)
-      const float x = ps[5 + k], tk = k == cls ? 1.f : 0.f, s = sigm(x);
-      cls_sum += (double)(a.cls_pw * tk * softplus(-x) + (1.f - tk) * softplus(x));
-      rec[7 + k] = -a.cls_pw * tk * (1.f - s) + (1.f - tk) * s;
+      const float x = ps[5 + k], tk = k == cls ? 1.f : 0.f;
+      if constexpr (FOCAL) {
+        float dx;
+        cls_sum += (double)focal_bce(x, tk, a.cls_pw, a.fl_gamma, &dx);
+        rec[7 + k] = dx;
+      } else {
+        const float s = sigm(x);
+        cls_sum += (double)(a.cls_pw * tk * softplus(-x) + (1.f - tk) * softplus(x));
+        rec[7 + k] = -a.cls_pw * tk * (1.f - s) + (1.f - tk) * s;
+      }
     }
   }
   atomicAdd(&a.sums[0], (double)(1.0f - ciou.v));
@@ -118,6 +150,7 @@ __global__ __launch_bounds__(128) void loss_candidates_kernel(const LossArgs a) 
   atomicMax(&a.winner[cell], c);
 }
 
+template <bool FOCAL>
 __global__ __launch_bounds__(256) void loss_obj_dense_kernel(const LossArgs a, long ncells) {
   const int RS = 7 + a.nc;
   const float gsc = a.h_obj * 4.0f * (float)a.B / (float)ncells;         // d(loss * bs) / d BCEobj-mean, balance[0] = 4 (loss.py:110)
@@ -127,11 +160,19 @@ __global__ __launch_bounds__(256) void loss_obj_dense_kernel(const LossArgs a, l
     const int w = a.winner[cell];
     float tobj = 0.f;
     if (w >= 0) tobj = (1.0f - a.gr) + a.gr * fmaxf(a.rec[(long)w * RS + 2], 0.f);      // :137
-    const float s = sigm(x);
-    part += (double)(a.obj_pw * tobj * softplus(-x) + (1.f - tobj) * softplus(x));
-    float* d = a.dpred + cell * a.no;
-    for (int k = 0; k < a.no; ++k) d[k] = 0.f;
-    d[4] = (-a.obj_pw * tobj * (1.f - s) + (1.f - tobj) * s) * gsc;
+    if constexpr (FOCAL) {
+      float dx;
+      part += (double)focal_bce(x, tobj, a.obj_pw, a.fl_gamma, &dx);
+      float* d = a.dpred + cell * a.no;
+      for (int k = 0; k < a.no; ++k) d[k] = 0.f;
+      d[4] = dx * gsc;
+    } else {
+      const float s = sigm(x);
+      part += (double)(a.obj_pw * tobj * softplus(-x) + (1.f - tobj) * softplus(x));
+      float* d = a.dpred + cell * a.no;
+      for (int k = 0; k < a.no; ++k) d[k] = 0.f;
+      d[4] = (-a.obj_pw * tobj * (1.f - s) + (1.f - tobj) * s) * gsc;
+    }
   }
   __shared__ double red[256];
   red[threadIdx.x] = part;
@@ -180,9 +221,11 @@ extern "C" int sodt_yolo_loss_workspace_bytes(long ncells, int nt, int nc, size_
   return SODT_OK;
 }
 
-extern "C" int sodt_yolo_loss(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx,
-                              int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr,
-                              void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st_) {
+namespace {
+
+int yolo_loss(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx, int nc,
+              float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr, float fl_gamma,
+              void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st_) {
   if (!pred || !anchors || !ws || !dpred || !out4 || B <= 0 || na <= 0 || na > 8 || ny <= 0 || nx <= 0 || nc < 1 || nc > LOSS_MAX_NC ||
       nt < 0 || (nt > 0 && !targets))
     return SODT_EINVAL;
@@ -198,14 +241,37 @@ extern "C" int sodt_yolo_loss(const float* pred, const float* targets, int nt, c
   a.rec = (float*)(w + win + 256);
   a.B = B; a.na = na; a.ny = ny; a.nx = nx; a.nc = nc; a.no = nc + 5; a.nt = nt;
   a.h_box = h_box; a.h_cls = h_cls; a.cls_pw = cls_pw; a.h_obj = h_obj; a.obj_pw = obj_pw; a.anchor_t = anchor_t; a.gr = gr;
+  a.fl_gamma = fl_gamma;
+  const bool focal = fl_gamma > 0.f;
   if (hipMemsetAsync(w, 0xff, win, st) != hipSuccess) return SODT_EINVAL;          // winner = -1
   if (hipMemsetAsync(w + win, 0, 256, st) != hipSuccess) return SODT_EINVAL;       // sums = 0
   const int ncand = 5 * na * nt;
-  if (ncand > 0) hipLaunchKernelGGL(loss_candidates_kernel, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
+  if (ncand > 0) {
+    if (focal) hipLaunchKernelGGL(loss_candidates_kernel<true>, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL(loss_candidates_kernel<false>, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
+  }
   long nb = (ncells + 255) / 256;
   if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(loss_obj_dense_kernel, dim3((unsigned)nb), dim3(256), 0, st, a, ncells);
+  if (focal) hipLaunchKernelGGL(loss_obj_dense_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, a, ncells);
+  else hipLaunchKernelGGL(loss_obj_dense_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, a, ncells);
   if (ncand > 0) hipLaunchKernelGGL(loss_scatter_kernel, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, st, a, ncells);
   return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+}
+
+}  // namespace
+
+extern "C" int sodt_yolo_loss(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx,
+                              int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr,
+                              void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st) {
+  return yolo_loss(pred, targets, nt, anchors, B, na, ny, nx, nc, h_box, h_cls, cls_pw, h_obj, obj_pw, anchor_t, gr, 0.f, ws, ws_bytes,
+                   dpred, out4, st);
+}
+
+extern "C" int sodt_yolo_loss_fl(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny,
+                                 int nx, int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t,
+                                 float gr, float fl_gamma, void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st) {
+  if (!(fl_gamma >= 0.f)) return SODT_EINVAL;
+  return yolo_loss(pred, targets, nt, anchors, B, na, ny, nx, nc, h_box, h_cls, cls_pw, h_obj, obj_pw, anchor_t, gr, fl_gamma, ws,
+                   ws_bytes, dpred, out4, st);
 }

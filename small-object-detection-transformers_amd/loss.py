@@ -4,9 +4,13 @@ objectness and class BCE and their gradient with respect to the head output in f
 signature and return tuple as the reference class, so ``compute_loss = ComputeLoss(model)`` /
 ``loss, lbox, lobj, lcls = compute_loss(pred, targets)`` (Train.py:281,418) port unchanged.
 
-Not carried over: focal loss (``fl_gamma > 0``) and ``autobalance`` (both off in models/hyp.scratch.yaml and
-Train.py:281) and label smoothing other than the reference's hard-coded ``smooth_BCE(eps=0.0)`` (loss.py:104); asking
-for them raises.
+``hyp['fl_gamma'] > 0`` (off in models/hyp.scratch.yaml, mutated in (0, 2] by ``--evolve``, Train.py:720) wraps the class
+and the objectness BCE in the reference's ``FocalLoss(BCEWithLogitsLoss(pos_weight), gamma, alpha=0.25)``
+(basics/utils/loss.py:36-62, :103-108), value and gradient, inside the same four launches (``sodt_yolo_loss_fl``);
+``fl_gamma == 0`` calls ``sodt_yolo_loss`` as before.
+
+Not carried over: ``autobalance`` (off in Train.py:281) and label smoothing other than the reference's hard-coded
+``smooth_BCE(eps=0.0)`` (loss.py:104); asking for them raises.
 """
 from __future__ import annotations
 
@@ -45,10 +49,11 @@ class _LossFn(torch.autograd.Function):
         if lib.sodt_yolo_loss_workspace_bytes(B * na * ny * nx, nt, nc, C.byref(nbytes)) != 0:
             raise RuntimeError("sodt_yolo_loss_workspace_bytes: unsupported shape (nc <= 32)")
         ws = torch.empty(nbytes.value, device=pred.device, dtype=torch.uint8)
-        ops._launch("sodt_yolo_loss", pred.data_ptr(), targets.data_ptr() if nt else None, nt, anchors.data_ptr(), B, na, ny, nx, nc,
-                    C.c_float(hyp["box"]), C.c_float(hyp["cls"]), C.c_float(hyp["cls_pw"]), C.c_float(hyp["obj"]),
-                    C.c_float(hyp["obj_pw"]), C.c_float(hyp["anchor_t"]), C.c_float(gr), ws.data_ptr(), nbytes.value,
-                    dpred.data_ptr(), out.data_ptr())
+        focal = hyp["fl_gamma"] > 0
+        ops._launch("sodt_yolo_loss_fl" if focal else "sodt_yolo_loss", pred.data_ptr(), targets.data_ptr() if nt else None, nt,
+                    anchors.data_ptr(), B, na, ny, nx, nc, C.c_float(hyp["box"]), C.c_float(hyp["cls"]), C.c_float(hyp["cls_pw"]),
+                    C.c_float(hyp["obj"]), C.c_float(hyp["obj_pw"]), C.c_float(hyp["anchor_t"]), C.c_float(gr),
+                    *((C.c_float(hyp["fl_gamma"]),) if focal else ()), ws.data_ptr(), nbytes.value, dpred.data_ptr(), out.data_ptr())
         ctx.save_for_backward(dpred)
         # independent tensors, not slices of `out`: views of one buffer returned by a multi-output Function are
         # MULTI_OUTPUT_NODE views on which the reference loop's in-place `loss *= opt.world_size` (Train.py:440),
@@ -69,8 +74,6 @@ class ComputeLoss:
         if autobalance:
             raise NotImplementedError("autobalance is off in the reference's training loop (Train.py:281)")
         h = model.hyp
-        if h.get("fl_gamma", 0.0) > 0:
-            raise NotImplementedError("focal loss (fl_gamma > 0) is not built; models/hyp.scratch.yaml uses 0")
         det = model.module.detect[-1] if hasattr(model, "module") else model.detect[-1]
         if det.nl != 1:
             raise NotImplementedError("one detection layer (models/model.yaml)")
@@ -89,4 +92,5 @@ class ComputeLoss:
         targets = targets.to(device=pred.device, dtype=torch.float32).contiguous()
         anchors = self.anchors[0].to(device=pred.device, dtype=torch.float32).contiguous()
         hyp = {k: float(self.hyp[k]) for k in ("box", "cls", "cls_pw", "obj", "obj_pw", "anchor_t")}
+        hyp["fl_gamma"] = float(self.hyp.get("fl_gamma", 0.0))      # read per call, like the rest: --evolve rewrites hyp
         return _LossFn.apply(pred, targets, anchors, hyp, float(self.gr), int(self.nc))

@@ -570,6 +570,18 @@ def sgd_ema_step(p, g, mom, ema, p_cast, group_of_chunk, lr, momentum, weight_de
             arr(lr), arr(momentum), arr(weight_decay), int(bool(nesterov)), C.c_float(grad_scale), C.c_float(ema_decay))
 
 
+def adam_ema_step(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr, betas, eps, weight_decay, decoupled, step,
+                  grad_scale=1.0, ema_decay=0.0):
+    """One fused Adam / AdamW (decoupled) + EMA + run-dtype cast pass over the flat buffers (csrc/optim.hip); per-group
+    hyper-parameters go down as doubles, `step` is torch's state['step'] after its increment (>= 1)."""
+    ng = len(lr)
+    arr = lambda v: (C.c_double * ng)(*[float(x) for x in v])
+    code = L.F32 if p_cast is None else dt_code(p_cast)
+    _launch("sodt_adam_ema_step", _p(p), _p(g), _p(exp_avg), _p(exp_avg_sq), _p(ema), _p(p_cast), code, _p(group_of_chunk),
+            p.numel(), ng, arr(lr), arr([b[0] for b in betas]), arr([b[1] for b in betas]), arr(eps), arr(weight_decay),
+            int(bool(decoupled)), int(step), C.c_float(grad_scale), C.c_float(ema_decay))
+
+
 def maxpool5_fwd(x, y, argmax, B, H, W, Cc, ldx=None, ldy=None, x_off=0, y_off=0):
     """y = MaxPool2d(5, 1, 2)(x), token-major; x / y may be channel slices of wider tensors (ld*, *_off in elements)."""
     es = x.element_size()

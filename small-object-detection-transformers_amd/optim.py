@@ -7,11 +7,15 @@ weight-decay groups of ``basics/optimizer.py:35-49`` (Train.py:139-150), calls `
 buffers of one layout, so all of it - plus the cast of the updated masters to the bf16 copy the GEMM kernels read - is
 ONE streaming kernel (csrc/optim.hip, ``sodt_sgd_ema_step``).
 
+``FusedAdam`` is the same for Train.py's ``--adam`` (Train.py:147-148: ``optim.Adam(pg0, lr=hyp['lr0'],
+betas=(hyp['momentum'], 0.999))``) and, with ``decoupled=True``, for the AdamW that ``basics/optimizer.py:11-33`` names:
+``sodt_adam_ema_step``, one launch with the same EMA and cast tail.
+
 ``FusedSGD`` is a ``torch.optim.Optimizer``: param groups, ``lr`` / ``momentum`` / ``weight_decay`` per group (the
 warm-up of Train.py:375-385 writes them every iteration), LR schedulers and ``zero_grad`` behave as with torch's SGD.
 ``ModelEMA`` mirrors the reference class (``.ema``, ``.updates``, ``.decay``, ``update``, ``update_attr``); attached to
-the optimizer (``FusedSGD(..., ema=ema)``) its parameter average rides in the fused kernel and ``ema.update(model)``
-only handles the few non-parameter buffers.
+the optimizer (``FusedSGD(..., ema=ema)`` / ``FusedAdam(..., ema=ema)``) its parameter average rides in the fused
+kernel and ``ema.update(model)`` only handles the few non-parameter buffers.
 """
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ class ModelEMA:
             p.requires_grad_(False)
         # the copy's own engine re-homes ITS parameters into a flat buffer of the same layout: that buffer is the average
         self.flat = self.ema._get_engine().flat_param
-        self._fused_pending = False        # set by FusedSGD.step when the parameter average was done in the fused kernel
+        self._fused_pending = False        # set by FusedSGD / FusedAdam.step when the parameter average was done in the fused kernel
 
     def next_decay(self) -> float:
         return self.decay(self.updates + 1)
@@ -81,26 +85,27 @@ class ModelEMA:
             setattr(self.ema, k, v)
 
 
-class FusedSGD(torch.optim.Optimizer):
-    """torch.optim.SGD(momentum, nesterov, weight_decay) semantics (dampening 0) over the engine's flat buffers."""
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What FusedSGD and FusedAdam share: the engine binding with the chunk -> group map, the skipped step when no backward
+    ran, the attached-EMA protocol and the freshness of the run-dtype mirror around the one kernel `_launch_step` issues."""
 
-    def __init__(self, params, model, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 0.0,
-                 nesterov: bool = True, ema: Optional[ModelEMA] = None):
-        if nesterov and momentum <= 0:
-            raise ValueError("Nesterov momentum requires a momentum")
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov))
+    _entry = ""            # the C entry, for messages
+    _n_state = 0           # flat f32 state buffers of the parameters' layout (momentum; exp_avg and exp_avg_sq)
+
+    def __init__(self, params, defaults, model, ema):
+        super().__init__(params, defaults)
         if len(self.param_groups) > 4:
-            raise ValueError("at most 4 parameter groups (sodt_sgd_ema_step)")
+            raise ValueError(f"at most 4 parameter groups ({self._entry})")
         self.model, self.ema = model, ema
         self._eng = None
-        self._mom = None
+        self._state = None
         self._groups = None
         self._sig = None
 
     def _bind(self):
         eng = self.model._get_engine()
         if eng is not self._eng:
-            self._eng, self._mom, self._sig = eng, torch.zeros_like(eng.flat_param), None
+            self._eng, self._state, self._sig = eng, [torch.zeros_like(eng.flat_param) for _ in range(self._n_state)], None
         sig = tuple(tuple(id(p) for p in g["params"]) for g in self.param_groups)
         if sig != self._sig:       # chunk -> group map (255: padding / parameters this optimizer does not own)
             gmap = torch.full((eng.flat_param.numel() // 4,), 255, dtype=torch.uint8)
@@ -108,7 +113,7 @@ class FusedSGD(torch.optim.Optimizer):
             for gi, g in enumerate(self.param_groups):
                 for p in g["params"]:
                     if id(p) not in off_of:
-                        raise ValueError("FusedSGD: a parameter does not belong to the model's engine")
+                        raise ValueError(f"{type(self).__name__}: a parameter does not belong to the model's engine")
                     o, n = off_of[id(p)]
                     gmap[o // 4: (o + n + 3) // 4] = gi
             self._groups, self._sig = gmap.to(eng.dev), sig
@@ -122,10 +127,7 @@ class FusedSGD(torch.optim.Optimizer):
         if eng._claim_grads():              # no backward since zero_grad(set_to_none=True): torch skips parameters without a gradient
             eng.flat_grad.zero_()
             return loss
-        gs = self.param_groups
-        nest = {bool(g["nesterov"]) for g in gs}
-        if len(nest) != 1:
-            raise ValueError("FusedSGD: nesterov must be the same for every group")
+        self._check_groups()
         ema_flat, d = None, 0.0
         if self.ema is not None:
             ema_eng = self.ema.ema._get_engine()
@@ -135,14 +137,41 @@ class FusedSGD(torch.optim.Optimizer):
             ema_flat, d = self.ema.flat, self.ema.next_decay()
             self.ema._fused_pending = True
         cast = next(iter(eng.flat_cast.values())) if eng.flat_cast else None
-        ops.sgd_ema_step(eng.flat_param, eng.flat_grad, self._mom, ema_flat, cast, self._groups,
-                         [g["lr"] for g in gs], [g["momentum"] for g in gs], [g["weight_decay"] for g in gs],
-                         nest.pop(), grad_scale, d)
+        self._launch_step(eng, ema_flat, cast, grad_scale, d)
         if cast is not None:
             eng.mark_cast_fresh()
         else:
             eng.invalidate_params()         # (no mirror to keep fresh; the engine still has to know the masters moved: _param_epoch)
         return loss
+
+    def _check_groups(self):
+        pass
+
+
+class FusedSGD(_FusedOptimizer):
+    """torch.optim.SGD(momentum, nesterov, weight_decay) semantics (dampening 0) over the engine's flat buffers."""
+
+    _entry, _n_state = "sodt_sgd_ema_step", 1
+
+    def __init__(self, params, model, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 0.0,
+                 nesterov: bool = True, ema: Optional[ModelEMA] = None):
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov), model, ema)
+
+    @property
+    def _mom(self):
+        return None if self._state is None else self._state[0]
+
+    def _check_groups(self):
+        if len({bool(g["nesterov"]) for g in self.param_groups}) != 1:
+            raise ValueError("FusedSGD: nesterov must be the same for every group")
+
+    def _launch_step(self, eng, ema_flat, cast, grad_scale, ema_decay):
+        gs = self.param_groups
+        ops.sgd_ema_step(eng.flat_param, eng.flat_grad, self._mom, ema_flat, cast, self._groups,
+                         [g["lr"] for g in gs], [g["momentum"] for g in gs], [g["weight_decay"] for g in gs],
+                         gs[0]["nesterov"], grad_scale, ema_decay)
 
     def state_dict(self):
         sd = super().state_dict()
@@ -156,3 +185,49 @@ class FusedSGD(torch.optim.Optimizer):
         if mom is not None:
             self._bind()
             self._mom.copy_(mom.to(self._mom.device))
+
+
+class FusedAdam(_FusedOptimizer):
+    """torch.optim.Adam (``decoupled=False``: weight decay added to the gradient, what Train.py:148 builds under --adam) or
+    torch.optim.AdamW (``decoupled=True``) semantics over the engine's flat buffers, ``amsgrad=False``.  ``lr``, ``betas``,
+    ``eps`` and ``weight_decay`` are read per group at every step.  One step counter serves every parameter: they all step
+    together, and a step without gradients advances nothing, as torch leaves ``state['step']`` of such parameters alone."""
+
+    _entry, _n_state = "sodt_adam_ema_step", 2
+
+    def __init__(self, params, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 amsgrad: bool = False, decoupled: bool = False, ema: Optional[ModelEMA] = None):
+        if amsgrad:
+            raise NotImplementedError("FusedAdam: amsgrad=True is not built (the reference never sets it)")
+        if not eps > 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), model, ema)
+        self.decoupled = bool(decoupled)
+        self._step = 0
+
+    def _launch_step(self, eng, ema_flat, cast, grad_scale, ema_decay):
+        gs = self.param_groups
+        ops.adam_ema_step(eng.flat_param, eng.flat_grad, self._state[0], self._state[1], ema_flat, cast, self._groups,
+                          [g["lr"] for g in gs], [g["betas"] for g in gs], [g["eps"] for g in gs],
+                          [g["weight_decay"] for g in gs], self.decoupled, self._step + 1, grad_scale, ema_decay)
+        self._step += 1                     # (after the launch: a refused one, e.g. a group's eps set to 0, is not a step)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        bound = self._state is not None
+        sd["exp_avg_flat"] = self._state[0].clone() if bound else None
+        sd["exp_avg_sq_flat"] = self._state[1].clone() if bound else None
+        sd["step"] = self._step
+        return sd
+
+    def load_state_dict(self, sd):
+        sd = dict(sd)                       # the caller's dict keeps its entries
+        m, v, step = sd.pop("exp_avg_flat", None), sd.pop("exp_avg_sq_flat", None), sd.pop("step", 0)
+        super().load_state_dict(sd)
+        self._step = int(step)
+        if m is not None and v is not None:
+            self._bind()
+            self._state[0].copy_(m.to(self._state[0].device))
+            self._state[1].copy_(v.to(self._state[1].device))
