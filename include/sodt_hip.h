@@ -459,6 +459,52 @@ int sodt_adam_ema_step(float* p, const float* g, float* exp_avg, float* exp_avg_
                        const double* beta1, const double* beta2, const double* eps, const double* weight_decay,
                        int decoupled, long step, float grad_scale, float ema_decay, sodt_stream_t st);
 
+/* The control path of the two fused steps (csrc/optim.hip): torch.amp.GradScaler (Train.py:285, :445-450: scaler.step(optimizer),
+ * scaler.update()), a skipped step when a gradient is not finite, and global-norm clipping (torch.nn.utils.clip_grad_norm_),
+ * with every decision taken on the device so that the host never waits.  sodt_grad_stats fills a 64-byte record in device
+ * memory (16-byte aligned) and the _ctl steps read it:
+ *   offset  0  double    acc_sumsq      work words of sodt_grad_stats: the entry zeroes these 16 bytes before its launch,
+ *           8  unsigned  acc_found      blocks touch them with device-scope atomics only
+ *          12  unsigned  ticket
+ *          16  double    sumsq          sum of squares of the owned gradient as stored (still scaled), accumulated in f64
+ *          24  double    grad_norm      sqrt(sumsq) * |grad_scale / scale|: the norm of the gradient the update sees, unclipped
+ *          32  long long step           applied updates so far; sodt_grad_stats adds 1 unless it sets skip.  The caller
+ *                                       initialises it (0 for a new optimizer) and may rewrite it between calls (resume)
+ *          40  float     found_inf      1 if an owned gradient element is inf / NaN or *found_inf_in != 0, else 0
+ *          44  float     inv_scale_eff  (float)(grad_scale / scale * clip_coef): what the step multiplies the gradient by
+ *          48  float     clip_coef      max_norm > 0: min(1, max_norm / (grad_norm + 1e-6)); else 1
+ *          52  int       skip           found_inf && skip_nonfinite
+ *          56  int       reserved[2] */
+typedef struct {
+  double acc_sumsq; unsigned acc_found, ticket;
+  double sumsq, grad_norm; long long step;
+  float found_inf, inv_scale_eff, clip_coef; int skip; int reserved[2];
+} sodt_step_ctl;
+
+/* One pass over g (n_elems f32, 16-byte aligned, n_elems % 4 == 0; group_of_chunk as in sodt_sgd_ema_step: chunks marked 255 are
+ * not owned and not read); the last block to finish finalises *ctl.  scale and found_inf_in are DEVICE pointers to one f32 each
+ * (GradScaler's own tensors), either may be null: scale null = 1, 1 / scale is formed as GradScaler forms it
+ * (double reciprocal rounded to f32); found_inf_in is OR-ed into found_inf.  grad_scale is the host factor of the plain
+ * entries and composes by multiplication.  max_norm <= 0: no clipping.  SODT_EINVAL: null / misaligned g or ctl (16 bytes),
+ * misaligned scale / found_inf_in (4 bytes), n_elems % 4, a NaN grad_scale or max_norm. */
+int sodt_grad_stats(const float* g, const unsigned char* group_of_chunk, long n_elems, const float* scale,
+                    const float* found_inf_in, float grad_scale, float max_norm, int skip_nonfinite, sodt_step_ctl* ctl,
+                    sodt_stream_t st);
+
+/* sodt_sgd_ema_step / sodt_adam_ema_step with grad_scale replaced by ctl->inv_scale_eff and, for Adam, step by ctl->step
+ * (lr / (1 - beta1^t) and sqrt(1 - beta2^t) are then formed in the kernel, in double from the double hyper-parameters).
+ * ctl->skip != 0: p, the momentum / exp_avg / exp_avg_sq are left as they are, while the EMA average and the run-dtype cast
+ * still run on the unchanged p (Train.py:450-453 calls ema.update after a skipped step too).  ctl is a DEVICE pointer that a
+ * sodt_grad_stats call earlier on the same stream has filled.  SODT_EINVAL additionally: a null or misaligned (16 bytes) ctl. */
+int sodt_sgd_ema_step_ctl(float* p, const float* g, float* mom, float* ema, void* p_cast, int cast_dtype,
+                          const unsigned char* group_of_chunk, long n_elems, int ngroups, const float* lr,
+                          const float* momentum, const float* weight_decay, int nesterov, const sodt_step_ctl* ctl,
+                          float ema_decay, sodt_stream_t st);
+int sodt_adam_ema_step_ctl(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* ema, void* p_cast, int cast_dtype,
+                           const unsigned char* group_of_chunk, long n_elems, int ngroups, const double* lr,
+                           const double* beta1, const double* beta2, const double* eps, const double* weight_decay,
+                           int decoupled, const sodt_step_ctl* ctl, float ema_decay, sodt_stream_t st);
+
 /* Input pre-processing of the training / evaluation loop (csrc/preprocess.hip): `imgs.to(device).float() / 255.0` followed by
  * `F.interpolate(image, size=[i // down_factor ...], mode='bilinear', align_corners=True)` (Train.py:364-374; test.py:124-129
  * is the factor-1 case) for the RGB and the IR batch in one launch.  rgb / ir: uint8 (B, c, Hin, Win) contiguous (device);

@@ -65,6 +65,14 @@ class GemmTnArgs(C.Structure):
                 ("partial", C.c_void_p), ("partial_floats", C.c_long)]
 
 
+class StepCtl(C.Structure):
+    """sodt_step_ctl (include/sodt_hip.h): the 64-byte device record sodt_grad_stats fills and the _ctl steps read."""
+    _fields_ = [("acc_sumsq", C.c_double), ("acc_found", C.c_uint), ("ticket", C.c_uint),
+                ("sumsq", C.c_double), ("grad_norm", C.c_double), ("step", C.c_longlong),
+                ("found_inf", C.c_float), ("inv_scale_eff", C.c_float), ("clip_coef", C.c_float), ("skip", C.c_int),
+                ("reserved", C.c_int * 2)]
+
+
 class PrepDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p),
                 ("d0", C.c_int), ("d1", C.c_int), ("d2", C.c_int),
@@ -128,6 +136,11 @@ SIGNATURES = {
                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _L, _F, _F, _P],
     "sodt_sgd_ema_step": [_P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                           _I, _F, _F, _P],
+    "sodt_grad_stats": [_P, _P, _L, _P, _P, _F, _F, _I, _P, _P],
+    "sodt_sgd_ema_step_ctl": [_P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                              C.POINTER(C.c_float), _I, _P, _F, _P],
+    "sodt_adam_ema_step_ctl": [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _F, _P],
     "sodt_preprocess_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],

@@ -582,6 +582,53 @@ def adam_ema_step(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr, be
             int(bool(decoupled)), int(step), C.c_float(grad_scale), C.c_float(ema_decay))
 
 
+def new_step_ctl(dev, step: int = 0):
+    """A zeroed sodt_step_ctl record in device memory as eight f64 words (L.StepCtl names the fields)."""
+    ctl = torch.zeros(C.sizeof(L.StepCtl) // 8, dtype=torch.float64, device=dev)
+    ctl.view(torch.int64)[L.StepCtl.step.offset // 8] = int(step)
+    return ctl
+
+
+def step_ctl_field(ctl, name):
+    """A one-element view of field `name` of a record made by new_step_ctl (no copy, no synchronisation)."""
+    f = getattr(L.StepCtl, name)
+    dt = {C.c_double: torch.float64, C.c_longlong: torch.int64, C.c_float: torch.float32, C.c_int: torch.int32,
+          C.c_uint: torch.int32}[dict((n, t) for n, t in L.StepCtl._fields_)[name]]
+    i = f.offset // f.size
+    return ctl.view(dt)[i:i + 1]
+
+
+def grad_stats(g, group_of_chunk, ctl, scale=None, found_inf=None, grad_scale=1.0, max_norm=None, skip_nonfinite=False):
+    """One pass over the flat gradient that fills the control record of the next *_step_ctl launch (csrc/optim.hip):
+    found_inf, the f64 norm, the clip coefficient, inv_scale_eff, the skip flag and the applied-step counter.  `scale` and
+    `found_inf` are one-element f32 DEVICE tensors (torch.amp.GradScaler's) or None; nothing is read on the host."""
+    for t in (scale, found_inf):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != g.device):
+            raise TypeError("grad_stats: scale / found_inf must be one-element float32 tensors on the gradient's device")
+    _launch("sodt_grad_stats", _p(g), _p(group_of_chunk), g.numel(), _p(scale), _p(found_inf), C.c_float(grad_scale),
+            C.c_float(0.0 if max_norm is None else max_norm), int(bool(skip_nonfinite)), _p(ctl))
+
+
+def sgd_ema_step_ctl(p, g, mom, ema, p_cast, group_of_chunk, lr, momentum, weight_decay, nesterov, ctl, ema_decay=0.0):
+    """sgd_ema_step with the gradient factor and the skip decision read from the device record `ctl` (grad_stats)."""
+    ng = len(lr)
+    arr = lambda v: (C.c_float * ng)(*[float(x) for x in v])
+    code = L.F32 if p_cast is None else dt_code(p_cast)
+    _launch("sodt_sgd_ema_step_ctl", _p(p), _p(g), _p(mom), _p(ema), _p(p_cast), code, _p(group_of_chunk), p.numel(), ng,
+            arr(lr), arr(momentum), arr(weight_decay), int(bool(nesterov)), _p(ctl), C.c_float(ema_decay))
+
+
+def adam_ema_step_ctl(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr, betas, eps, weight_decay, decoupled, ctl,
+                      ema_decay=0.0):
+    """adam_ema_step with the gradient factor, the skip decision and the step count t read from the device record `ctl`."""
+    ng = len(lr)
+    arr = lambda v: (C.c_double * ng)(*[float(x) for x in v])
+    code = L.F32 if p_cast is None else dt_code(p_cast)
+    _launch("sodt_adam_ema_step_ctl", _p(p), _p(g), _p(exp_avg), _p(exp_avg_sq), _p(ema), _p(p_cast), code, _p(group_of_chunk),
+            p.numel(), ng, arr(lr), arr([b[0] for b in betas]), arr([b[1] for b in betas]), arr(eps), arr(weight_decay),
+            int(bool(decoupled)), _p(ctl), C.c_float(ema_decay))
+
+
 def maxpool5_fwd(x, y, argmax, B, H, W, Cc, ldx=None, ldy=None, x_off=0, y_off=0):
     """y = MaxPool2d(5, 1, 2)(x), token-major; x / y may be channel slices of wider tensors (ld*, *_off in elements)."""
     es = x.element_size()

@@ -16,6 +16,19 @@ warm-up of Train.py:375-385 writes them every iteration), LR schedulers and ``ze
 ``ModelEMA`` mirrors the reference class (``.ema``, ``.updates``, ``.decay``, ``update``, ``update_attr``); attached to
 the optimizer (``FusedSGD(..., ema=ema)`` / ``FusedAdam(..., ema=ema)``) its parameter average rides in the fused
 kernel and ``ema.update(model)`` only handles the few non-parameter buffers.
+
+The control path.  Both optimizers declare ``_step_supports_amp_scaling``, so ``torch.amp.GradScaler.step`` (Train.py:285,
+:445-450) hands its scale and found-inf DEVICE tensors to ``step()`` instead of unscaling 273 gradient views and reading
+``found_inf`` on the host.  ``step()`` then issues two launches: ``sodt_grad_stats`` (one pass over the flat gradient that
+leaves found_inf, the f64 gradient norm, the clip coefficient and the effective gradient factor in a small device record)
+and the ``_ctl`` sibling of the step kernel, which reads that record.  The same path serves ``skip_nonfinite=True`` (a
+step whose gradient holds an inf / NaN changes neither parameters nor optimizer state; the EMA average and the run-dtype
+mirror still run, as ``ema.update`` after a skipped ``scaler.step`` does in the reference) and ``max_grad_norm``
+(``torch.nn.utils.clip_grad_norm_`` over every owned parameter, applied to the unscaled gradient).  No host read happens
+on this path.  With neither option and no scaler, ``step()`` is the one launch it always was.
+
+Data parallel: ``ddp.attach`` all-reduces the flat gradient before the step, so every rank sees the same gradient and
+takes the same skip and clip decisions; no collective is added for them.
 """
 from __future__ import annotations
 
@@ -91,12 +104,18 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     _entry = ""            # the C entry, for messages
     _n_state = 0           # flat f32 state buffers of the parameters' layout (momentum; exp_avg and exp_avg_sq)
+    _step_supports_amp_scaling = True      # GradScaler.step sets .grad_scale / .found_inf (device tensors) and calls step()
 
-    def __init__(self, params, defaults, model, ema):
+    def __init__(self, params, defaults, model, ema, max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (a positive number, or None for no clipping)")
         super().__init__(params, defaults)
         if len(self.param_groups) > 4:
             raise ValueError(f"at most 4 parameter groups ({self._entry})")
         self.model, self.ema = model, ema
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._ctl = None           # the device control record (ops.new_step_ctl), made at the first control-path step
         self._eng = None
         self._state = None
         self._groups = None
@@ -137,7 +156,17 @@ class _FusedOptimizer(torch.optim.Optimizer):
             ema_flat, d = self.ema.flat, self.ema.next_decay()
             self.ema._fused_pending = True
         cast = next(iter(eng.flat_cast.values())) if eng.flat_cast else None
-        self._launch_step(eng, ema_flat, cast, grad_scale, d)
+        # torch.amp.GradScaler.step sets these two attributes around its call of step(): the scale (None after
+        # scaler.unscale_: the gradients are already unscaled) and the found-inf sum, both f32 tensors on the device
+        amp_scale, amp_found = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        amp = amp_scale is not None or amp_found is not None
+        if amp or self.skip_nonfinite or self.max_grad_norm is not None:
+            ctl = self._ctl_record(eng)
+            ops.grad_stats(eng.flat_grad, self._groups, ctl, amp_scale, amp_found, grad_scale, self.max_grad_norm,
+                           amp or self.skip_nonfinite)
+            self._launch_step_ctl(eng, ema_flat, cast, ctl, d)
+        else:
+            self._launch_step(eng, ema_flat, cast, grad_scale, d)
         if cast is not None:
             eng.mark_cast_fresh()
         else:
@@ -147,6 +176,19 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def _check_groups(self):
         pass
 
+    def _ctl_record(self, eng):
+        if self._ctl is None or self._ctl.device != eng.flat_grad.device:
+            self._ctl = ops.new_step_ctl(eng.flat_grad.device)
+        return self._ctl
+
+    def last_step_info(self):
+        """``(found_inf, grad_norm)`` of the last control-path step as one-element DEVICE tensors (f32 0 / 1; f64 norm of the
+        unscaled gradient before clipping), or ``(None, None)`` before the first one.  Copies made on the device: reading
+        them later (``.item()`` at a logging interval) is the caller's synchronisation, this call forces none."""
+        if self._ctl is None:
+            return None, None
+        return ops.step_ctl_field(self._ctl, "found_inf").clone(), ops.step_ctl_field(self._ctl, "grad_norm").clone()
+
 
 class FusedSGD(_FusedOptimizer):
     """torch.optim.SGD(momentum, nesterov, weight_decay) semantics (dampening 0) over the engine's flat buffers."""
@@ -154,10 +196,12 @@ class FusedSGD(_FusedOptimizer):
     _entry, _n_state = "sodt_sgd_ema_step", 1
 
     def __init__(self, params, model, lr: float = 0.01, momentum: float = 0.937, weight_decay: float = 0.0,
-                 nesterov: bool = True, ema: Optional[ModelEMA] = None):
+                 nesterov: bool = True, ema: Optional[ModelEMA] = None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum")
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov), model, ema)
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov), model, ema,
+                         max_grad_norm, skip_nonfinite)
 
     @property
     def _mom(self):
@@ -172,6 +216,12 @@ class FusedSGD(_FusedOptimizer):
         ops.sgd_ema_step(eng.flat_param, eng.flat_grad, self._mom, ema_flat, cast, self._groups,
                          [g["lr"] for g in gs], [g["momentum"] for g in gs], [g["weight_decay"] for g in gs],
                          gs[0]["nesterov"], grad_scale, ema_decay)
+
+    def _launch_step_ctl(self, eng, ema_flat, cast, ctl, ema_decay):
+        gs = self.param_groups
+        ops.sgd_ema_step_ctl(eng.flat_param, eng.flat_grad, self._mom, ema_flat, cast, self._groups,
+                             [g["lr"] for g in gs], [g["momentum"] for g in gs], [g["weight_decay"] for g in gs],
+                             gs[0]["nesterov"], ctl, ema_decay)
 
     def state_dict(self):
         sd = super().state_dict()
@@ -191,21 +241,52 @@ class FusedAdam(_FusedOptimizer):
     """torch.optim.Adam (``decoupled=False``: weight decay added to the gradient, what Train.py:148 builds under --adam) or
     torch.optim.AdamW (``decoupled=True``) semantics over the engine's flat buffers, ``amsgrad=False``.  ``lr``, ``betas``,
     ``eps`` and ``weight_decay`` are read per group at every step.  One step counter serves every parameter: they all step
-    together, and a step without gradients advances nothing, as torch leaves ``state['step']`` of such parameters alone."""
+    together, and a step without gradients advances nothing, as torch leaves ``state['step']`` of such parameters alone.
+    On the control path the counter lives in the device record and advances only when the step is applied, so the step after
+    a skipped one takes the bias correction of t, not t + 1; ``_step`` (and ``state_dict()['step']``) read it back, which
+    synchronises - at checkpoint time, not in the loop."""
 
     _entry, _n_state = "sodt_adam_ema_step", 2
 
     def __init__(self, params, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, decoupled: bool = False, ema: Optional[ModelEMA] = None):
+                 amsgrad: bool = False, decoupled: bool = False, ema: Optional[ModelEMA] = None,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         if amsgrad:
             raise NotImplementedError("FusedAdam: amsgrad=True is not built (the reference never sets it)")
         if not eps > 0.0:
             raise ValueError(f"Invalid epsilon value: {eps}")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"Invalid beta parameters: {betas}")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), model, ema)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), model, ema, max_grad_norm,
+                         skip_nonfinite)
         self.decoupled = bool(decoupled)
-        self._step = 0
+        self._step_host = 0        # the count as the host knows it; stale while _step_on_device
+        self._step_on_device = False
+
+    @property
+    def _step(self) -> int:
+        if self._step_on_device:            # control-path steps advanced (or skipped) on the device since the last read
+            self._step_host = int(ops.step_ctl_field(self._ctl, "step").item())
+            self._step_on_device = False
+        return self._step_host
+
+    @_step.setter
+    def _step(self, v: int):
+        self._step_host, self._step_on_device = int(v), False
+        if self._ctl is not None:
+            ops.step_ctl_field(self._ctl, "step").fill_(int(v))
+
+    def _ctl_record(self, eng):
+        if self._ctl is None or self._ctl.device != eng.flat_grad.device:
+            self._ctl = ops.new_step_ctl(eng.flat_grad.device, self._step)
+        return self._ctl
+
+    def _launch_step_ctl(self, eng, ema_flat, cast, ctl, ema_decay):
+        gs = self.param_groups
+        ops.adam_ema_step_ctl(eng.flat_param, eng.flat_grad, self._state[0], self._state[1], ema_flat, cast, self._groups,
+                              [g["lr"] for g in gs], [g["betas"] for g in gs], [g["eps"] for g in gs],
+                              [g["weight_decay"] for g in gs], self.decoupled, ctl, ema_decay)
+        self._step_on_device = True
 
     def _launch_step(self, eng, ema_flat, cast, grad_scale, ema_decay):
         gs = self.param_groups
