@@ -410,7 +410,19 @@ int sodt_nms_select(const float* z, int nc, const unsigned long long* keys, long
  *   [nc_u, bad target classes, rows of tp with any true entry, argmax index].  Predictions are ordered by descending
  *   confidence with ties in row order (a stable sort; the reference's np.argsort(-conf) leaves ties unordered).
  *   ws: scratch of at least sodt_ap_per_class_workspace_bytes(n, nt, nc).
- * Neither entry allocates or synchronises. */
+ * sodt_confusion_update: ConfusionMatrix.process_batch (metrics.py:117-155) for every image of a batch at once.
+ *   det / det_off / targets / geom as sodt_eval_match.  geom may be NULL: the boxes are then taken as they are and
+ *   targets rows are [img cls x1 y1 x2 y2] (process_batch's own arguments, already in native pixels).  nc <= 4096;
+ *   conf / iou_thres: host floats, both compared strictly (conf > conf, iou > iou_thres).
+ *   matrix: device int64[(nc+1)*(nc+1)], row-major, ADDED into.  Per image, box_iou(labels, detections) of the kept
+ *   detections bit for bit as above; every detection keeps its highest-IoU pair, then every label its highest-IoU pair
+ *   among those (equal IoU: the lower label index, then the lower detection index; unspecified in the reference).
+ *   A label with a pair counts at [gt class, detection class], any other label at [nc, gt class]; a kept detection
+ *   without a surviving pair counts at [detection class, nc] only when the image has at least one pair (metrics.py:152).
+ *   Pair indices are int32 (the reference's int16 wraps above 32767 rows per image).  info: device int32[2], ADDED
+ *   into: [labels, kept detections] whose class is not an integral value in [0, nc); a count that needs such a class
+ *   is not written.  ws: scratch of at least sodt_confusion_update_workspace_bytes(B, n_det, nt).
+ * No entry allocates or synchronises. */
 int sodt_eval_match_workspace_bytes(int B, long n_det, long nt, size_t* bytes);
 int sodt_eval_match(const float* det, const int* det_off, int B, long n_det, const float* targets, long nt,
                     const float* geom, const float* iouv, void* ws, size_t ws_bytes, unsigned char* correct,
@@ -419,6 +431,10 @@ int sodt_ap_per_class_workspace_bytes(long n, long nt, int nc, size_t* bytes);
 int sodt_ap_per_class(const unsigned char* tp, const float* conf, const float* pred_cls, long n, const float* target_cls,
                       long nt, int nc, void* ws, size_t ws_bytes, double* p, double* r, double* f1, double* ap,
                       int* classes, int* nt_count, int* info, sodt_stream_t st);
+int sodt_confusion_update_workspace_bytes(int B, long n_det, long nt, size_t* bytes);
+int sodt_confusion_update(const float* det, const int* det_off, int B, long n_det, const float* targets, long nt,
+                          const float* geom, int nc, float conf, float iou_thres, void* ws, size_t ws_bytes,
+                          long long* matrix, int* info, sodt_stream_t st);
 
 /* Batched parameter preparation: out = cast(permute3(in)) for a device-resident table. */
 typedef struct {

@@ -96,6 +96,8 @@ SIGNATURES = {
     "sodt_eval_match": [_P, _P, _I, _L, _P, _L, _P, C.POINTER(C.c_float), _P, C.c_size_t, _P, _P, _P],
     "sodt_ap_per_class_workspace_bytes": [_L, _L, _I, C.POINTER(C.c_size_t)],
     "sodt_ap_per_class": [_P, _P, _P, _L, _P, _L, _I, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sodt_confusion_update_workspace_bytes": [_I, _L, _L, C.POINTER(C.c_size_t)],
+    "sodt_confusion_update": [_P, _P, _I, _L, _P, _L, _P, _I, _F, _F, _P, C.c_size_t, _P, _P, _P],
     "sodt_gemm_nt": [C.POINTER(GemmArgs), _I, _P],
     "sodt_gemm_tn": [C.POINTER(GemmTnArgs), _I, _P],
     "sodt_layernorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],

@@ -26,6 +26,15 @@
 //                   precision envelope (backward, compute_ap's reversed np.maximum.accumulate)
 //   ap_curves     : one workgroup per class: r / p at the 1000 points of np.linspace(0, 1, 1000) and the 10 APs
 //   ap_finalize   : f1, the first argmax of f1.mean(0), p / r / f1 at that index
+//
+// sodt_confusion_update (ConfusionMatrix.process_batch, metrics.py:117-155, for a whole batch):
+//   match_keys / radix sort / match_offsets as above, then
+//   confusion_image : one workgroup per image over IoU tiles in LDS.  The reference's two "sort by IoU, np.unique"
+//                   passes are two argmax reductions: per detection over its labels, then per label over the
+//                   detections that kept it.  Each is an atomicMax on a (IoU bits, ~index) word, so equal IoUs go to
+//                   the lower label, then the lower detection (the reference's argsort leaves them unordered).  The
+//                   counts go through an LDS histogram into an integer matrix: the result does not depend on the order
+//                   of images or of workgroups.
 #pragma clang fp contract(off)
 #include <climits>
 #include <rocprim/block/block_scan.hpp>
@@ -507,6 +516,150 @@ int ap_layout_of(long n, long nt, int nc, ap_layout& L) {
   return SODT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// confusion matrix
+
+constexpr int CF_LT = 64;       // labels of one LDS tile: one per lane of a wave
+constexpr int CF_DT = 256;      // detections of one LDS tile
+constexpr int CF_HIST = 8192;   // a matrix of up to this many cells (nc <= 89) is counted in LDS first
+
+// the float bits made monotonic: a < b  <=>  asc_bits(a) < asc_bits(b) for non-NaN a, b
+__device__ __forceinline__ uint32_t asc_bits(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// A candidate pair as one word for atomicMax: the higher IoU wins, then the lower index of the other side.  Never 0.
+__device__ __forceinline__ unsigned long long pair_key(uint32_t iou_bits, int other) {
+  return ((unsigned long long)iou_bits << 32) | (0xFFFFFFFFu - (uint32_t)other);
+}
+__device__ __forceinline__ int key_index(unsigned long long k) { return (int)(0xFFFFFFFFu - (uint32_t)k); }
+// keys are written by atomics at L2; read them there too
+__device__ __forceinline__ unsigned long long key_load(const unsigned long long* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One workgroup per image.  IoU tiles of CF_DT detections x CF_LT labels: lane l of every wave holds label l of the
+// tile in registers, the waves stride over the tile's detections (a wave-uniform LDS read).
+//   1. column reduction: dkey[p] = max over the image's labels of pair_key(iou, label), iou > iou_thres
+//   2. row reduction over the survivors: lkey[t] = max over detections whose best label is t of pair_key(iou, p)
+//   3. labels: matched -> [gc, dc], else [nc, gc]
+//   4. if any label matched: kept detections that are not their label's winner -> [dc, nc]
+__global__ __launch_bounds__(TPB) void confusion_image_kernel(
+    const float* __restrict__ det, const int* __restrict__ det_off, int n_det, const float* __restrict__ tg,
+    const uint32_t* __restrict__ trow, const int* __restrict__ toff, const float* __restrict__ geom, int nc, float conf,
+    float iou_thres, float4* __restrict__ tbox, unsigned long long* __restrict__ dkey, unsigned long long* __restrict__ lkey,
+    unsigned long long* __restrict__ matrix, int* __restrict__ info) {
+  __shared__ float4 s_det[CF_DT];
+  __shared__ float4 s_lab[CF_LT];
+  __shared__ unsigned char s_keep[CF_DT];
+  __shared__ int s_hist[CF_HIST];
+  __shared__ int s_any;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n1 = nc + 1, cells = n1 * n1;
+  const bool hist = cells <= CF_HIST;
+  const float* g = geom ? geom + (long)b * 5 : nullptr;
+  const int t0 = toff[b], t1 = toff[b + 1];
+  const int d0 = min(max(det_off[b], 0), n_det), d1 = min(max(det_off[b + 1], d0), n_det);
+  auto count = [&](int r, int c) {   // a class outside [0, nc) arrives as -1: reported in info, never written
+    if (r < 0 || c < 0) return;
+    if (hist) atomicAdd(&s_hist[r * n1 + c], 1);
+    else atomicAdd(&matrix[(long)r * n1 + c], 1ull);
+  };
+
+  if (hist) for (int i = tid; i < cells; i += TPB) s_hist[i] = 0;
+  if (tid == 0) s_any = 0;
+  for (int t = t0 + tid; t < t1; t += TPB) {
+    const float* r = tg + (long)trow[t] * 6;
+    // with geometry: xywh2xyxy then scale_coords, as match_image_kernel; without: the row holds x1 y1 x2 y2 as they are
+    tbox[t] = g ? scale_box(r[2] - r[4] / 2, r[3] - r[5] / 2, r[2] + r[4] / 2, r[3] + r[5] / 2, g)
+                : make_float4(r[2], r[3], r[4], r[5]);
+    lkey[t] = 0;
+  }
+  for (int p = d0 + tid; p < d1; p += TPB) dkey[p] = 0;
+
+  for (int dt = d0; dt < d1; dt += CF_DT) {
+    const int nd = min(CF_DT, d1 - dt);
+    __syncthreads();   // the previous tile has been consumed; the first time: tbox / dkey / lkey are written
+    if (tid < nd) {
+      const float* r = det + (long)(dt + tid) * 6;
+      s_det[tid] = g ? scale_box(r[0], r[1], r[2], r[3], g) : make_float4(r[0], r[1], r[2], r[3]);
+      s_keep[tid] = r[4] > conf;   // metrics.py:127, strict
+    }
+    for (int lt = t0; lt < t1; lt += CF_LT) {
+      const int nl = min(CF_LT, t1 - lt);
+      __syncthreads();
+      if (tid < nl) s_lab[tid] = tbox[lt + tid];
+      __syncthreads();
+      const int l = tid & (CF_LT - 1);
+      if (l < nl) {
+        const float4 lb = s_lab[l];
+        for (int d = tid / CF_LT; d < nd; d += TPB / CF_LT) {
+          if (!s_keep[d]) continue;
+          const float v = box_iou1(lb, s_det[d]);   // box_iou(labels, detections), metrics.py:130
+          if (v > iou_thres) atomicMax(&dkey[dt + d], pair_key(asc_bits(v), lt + l));
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int p = d0 + tid; p < d1; p += TPB) {
+    const unsigned long long k = key_load(&dkey[p]);
+    if (k) atomicMax(&lkey[key_index(k)], pair_key((uint32_t)(k >> 32), p));
+  }
+  __syncthreads();
+  for (int t = t0 + tid; t < t1; t += TPB) {
+    const int gc = class_id(tg[(long)trow[t] * 6 + 1], nc);
+    if (gc < 0) atomicAdd(&info[0], 1);
+    const unsigned long long k = key_load(&lkey[t]);
+    if (k) {
+      s_any = 1;
+      count(gc, class_id(det[(long)key_index(k) * 6 + 5], nc));   // metrics.py:148
+    } else {
+      count(nc, gc);                                              // metrics.py:150
+    }
+  }
+  __syncthreads();
+  const bool any = s_any != 0;   // metrics.py:152, `if n:`
+  for (int p = d0 + tid; p < d1; p += TPB) {
+    const float* r = det + (long)p * 6;
+    if (!(r[4] > conf)) continue;
+    const int dc = class_id(r[5], nc);
+    if (dc < 0) atomicAdd(&info[1], 1);
+    const unsigned long long k = key_load(&dkey[p]);
+    const bool won = k && key_index(key_load(&lkey[key_index(k)])) == p;
+    if (any && !won) count(dc, nc);                               // metrics.py:155
+  }
+  if (!hist) return;
+  __syncthreads();
+  for (int i = tid; i < cells; i += TPB) {
+    const int v = s_hist[i];
+    if (v) atomicAdd(&matrix[i], (unsigned long long)v);
+  }
+}
+
+struct confusion_layout { size_t keys_in, keys_out, rows_in, rows_out, sort_tmp, sort_tmp_bytes, toff, tbox, dkey, lkey, total; };
+
+int confusion_layout_of(int B, long n_det, long nt, confusion_layout& L) {
+  if (B <= 0 || n_det < 0 || nt < 0 || n_det > MAX_ROWS || nt > MAX_ROWS) return SODT_EINVAL;
+  size_t tb = 0;
+  if (nt > 0 && rocprim::radix_sort_pairs<rocprim::default_config, const uint32_t*, uint32_t*, const uint32_t*, uint32_t*>(
+                    nullptr, tb, nullptr, nullptr, nullptr, nullptr, (size_t)nt, 0, bits_for((unsigned long)B)) != hipSuccess)
+    return SODT_EINVAL;
+  size_t o = 0;
+  L.keys_in = o; o += align256((size_t)nt * 4);
+  L.keys_out = o; o += align256((size_t)nt * 4);
+  L.rows_in = o; o += align256((size_t)nt * 4);
+  L.rows_out = o; o += align256((size_t)nt * 4);
+  L.sort_tmp = o; L.sort_tmp_bytes = tb; o += align256(tb);
+  L.toff = o; o += align256((size_t)(B + 1) * 4);
+  L.tbox = o; o += align256((size_t)nt * 16);
+  L.dkey = o; o += align256((size_t)n_det * 8);
+  L.lkey = o; o += align256((size_t)nt * 8);
+  L.total = o;
+  return SODT_OK;
+}
+
 }  // namespace
 
 extern "C" int sodt_eval_match_workspace_bytes(int B, long n_det, long nt, size_t* bytes) {
@@ -592,5 +745,40 @@ extern "C" int sodt_ap_per_class(const unsigned char* tp, const float* conf, con
   if (n > 0) ap_scan_kernel<<<nc, TPB, 0, stream>>>(tp, conf, rows_out, seg, n_l, tpc, env, conf_s);
   ap_curves_kernel<<<nc, TPB, 0, stream>>>(seg, n_l, ci_of, tpc, env, conf_s, pc, rc, ap);
   ap_finalize_kernel<<<1, 1024, 0, stream>>>(pc, rc, info, p, r, f1);
+  return SODT_OK;
+}
+
+extern "C" int sodt_confusion_update_workspace_bytes(int B, long n_det, long nt, size_t* bytes) {
+  confusion_layout L;
+  if (!bytes || confusion_layout_of(B, n_det, nt, L) != SODT_OK) return SODT_EINVAL;
+  *bytes = L.total;
+  return SODT_OK;
+}
+
+extern "C" int sodt_confusion_update(const float* det, const int* det_off, int B, long n_det, const float* targets, long nt,
+                                     const float* geom, int nc, float conf, float iou_thres, void* ws, size_t ws_bytes,
+                                     long long* matrix, int* info, hipStream_t stream) {
+  confusion_layout L;
+  if (!det_off || !ws || !matrix || !info || (n_det > 0 && !det) || (nt > 0 && !targets) || nc <= 0 || nc > MAX_CLASSES)
+    return SODT_EINVAL;
+  if (confusion_layout_of(B, n_det, nt, L) != SODT_OK || ws_bytes < L.total) return SODT_EINVAL;
+  char* base = (char*)ws;
+  uint32_t* keys_in = (uint32_t*)(base + L.keys_in);
+  uint32_t* keys_out = (uint32_t*)(base + L.keys_out);
+  uint32_t* rows_in = (uint32_t*)(base + L.rows_in);
+  uint32_t* rows_out = (uint32_t*)(base + L.rows_out);
+  int* toff = (int*)(base + L.toff);
+  const int ntt = (int)nt;
+  if (ntt > 0) {   // group the targets by image exactly as sodt_eval_match does: a stable sort keeps each image's row order
+    match_keys_kernel<<<(ntt + 255) / 256, 256, 0, stream>>>(targets, ntt, B, keys_in, rows_in);
+    size_t tb = L.sort_tmp_bytes;
+    if (rocprim::radix_sort_pairs(base + L.sort_tmp, tb, (const uint32_t*)keys_in, keys_out, (const uint32_t*)rows_in,
+                                  rows_out, (size_t)ntt, 0, bits_for((unsigned long)B), stream) != hipSuccess)
+      return SODT_EINVAL;
+  }
+  match_offsets_kernel<<<(B + 1 + 255) / 256, 256, 0, stream>>>(keys_out, ntt, B, toff);
+  confusion_image_kernel<<<B, TPB, 0, stream>>>(det, det_off, (int)n_det, targets, rows_out, toff, geom, nc, conf, iou_thres,
+                                                (float4*)(base + L.tbox), (unsigned long long*)(base + L.dkey),
+                                                (unsigned long long*)(base + L.lkey), (unsigned long long*)matrix, info);
   return SODT_OK;
 }

@@ -1,11 +1,13 @@
 """Validation statistics on the GPU - the drop-ins for the per-image true-positive matching and the mAP of
-`basics/test.py:155-264` and for `ap_per_class` (`basics/utils/metrics.py:18-78`).
+`basics/test.py:155-264`, for `ap_per_class` (`basics/utils/metrics.py:18-78`) and for `ConfusionMatrix`
+(`basics/utils/metrics.py:109-158`).
 
 Everything after NMS runs in HIP kernels (csrc/metrics.hip) behind the C ABI (`sodt_eval_match`,
-`sodt_ap_per_class`): `DetectionMetrics.update` launches one matching pass per batch and appends to device
-buffers without synchronising (non_max_suppression has already read the per-image counts, so packing the batch
-needs no device read); `compute()` runs ap_per_class on the device and synchronises once.  torch only allocates
-and packs here.
+`sodt_ap_per_class`, `sodt_confusion_update`): `DetectionMetrics.update` launches one matching pass per batch and
+appends to device buffers without synchronising (non_max_suppression has already read the per-image counts, so
+packing the batch needs no device read); `compute()` runs ap_per_class on the device and synchronises once.
+`ConfusionMatrix.update` / `.process_batch` add into a device matrix the same way; `.matrix` synchronises once.
+torch only allocates and packs here.
 
 Differences from the reference, documented in DESIGN.md:
   * predictions with equal confidence keep their row order (a stable sort); the reference's np.argsort(-conf) is
@@ -13,6 +15,11 @@ Differences from the reference, documented in DESIGN.md:
   * `plot=True` raises NotImplementedError: the PR / F1 curves are not drawn.
   * classes are integral values below 4096; a target row whose image index is not in the batch takes part in no
     statistic, as in the reference.
+  * ConfusionMatrix: candidate pairs with equal IoU go to the lower label index, then the lower detection index; the
+    reference's `matches[:, 2].argsort()[::-1]` is not stable, so its winner among equal IoUs is unspecified.
+  * ConfusionMatrix: pair indices are int32.  The reference casts them to int16 (metrics.py:144), which wraps above
+    32,767 labels or detections per image; below that the two agree (NMS keeps at most 300 detections).
+  * ConfusionMatrix.plot raises NotImplementedError; `normalized()` returns the array it would draw.
 """
 from __future__ import annotations
 
@@ -192,3 +199,110 @@ class DetectionMetrics:
         for i, c in enumerate(ap_class):
             maps[c] = apm[i]
         return DetectionResult(mp, mr, map50, map_, maps, nt, p, r, ap50, apm, ap_class.astype(np.int32))
+
+
+def _pack(out: Sequence[torch.Tensor], dev):
+    """The NMS list as packed (n_det, 6) f32 rows and (B+1) int32 device offsets; the counts are host shapes."""
+    off = np.zeros(len(out) + 1, dtype=np.int32)
+    np.cumsum([int(o.shape[0]) for o in out], out=off[1:])
+    det = (torch.cat([o.detach().to(dev, torch.float32).view(-1, 6) for o in out]) if int(off[-1])
+           else torch.zeros((0, 6), dtype=torch.float32, device=dev)).contiguous()
+    return det, torch.from_numpy(off).pin_memory().to(dev, non_blocking=True)
+
+
+class ConfusionMatrix:
+    """metrics.py:109-158 on the GPU, with the reference's constructor.  Rows are predicted classes, columns true
+    classes, index nc is the background, exactly as the reference fills them.
+
+        confusion_matrix = ConfusionMatrix(nc)
+        for ...:
+            out = non_max_suppression(...)
+            confusion_matrix.update(out, targets, img.shape[2:], shapes)   # DetectionMetrics.update's arguments
+        confusion_matrix.matrix                                            # numpy (nc+1, nc+1) f64, one synchronisation
+    """
+
+    def __init__(self, nc: int, conf: float = 0.25, iou_thres: float = 0.45, device=None):
+        if not 1 <= int(nc) <= MAX_CLASSES:
+            raise ValueError(f"nc must be in [1, {MAX_CLASSES}], got {nc}")
+        self.nc, self.conf, self.iou_thres = int(nc), conf, iou_thres
+        self.device = _device() if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ConfusionMatrix runs on the GPU (there is no CPU fallback)")
+        self._matrix = torch.zeros((self.nc + 1) ** 2, dtype=torch.int64, device=self.device)
+        self._info = torch.zeros(2, dtype=torch.int32, device=self.device)
+
+    def reset(self) -> None:
+        self._matrix.zero_()
+        self._info.zero_()
+
+    def _launch(self, det, off, tg, geom) -> None:
+        ws = torch.empty(max(1, ops.confusion_workspace_bytes(off.numel() - 1, det.shape[0], tg.shape[0])),
+                         dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            ops.confusion_update(det, off, tg, geom, self.nc, self.conf, self.iou_thres, ws, self._matrix, self._info)
+
+    def process_batch(self, detections: torch.Tensor, labels: torch.Tensor) -> None:
+        """The reference's per-image call (test.py:216): detections (N, 6) [x1 y1 x2 y2 conf cls] and labels (M, 5)
+        [cls x1 y1 x2 y2], both already in native pixels.  The boxes are used as they are."""
+        dev = self.device
+        det, off = _pack([detections.reshape(-1, 6)], dev)
+        lab = labels.detach().to(dev, torch.float32).reshape(-1, 5)
+        tg = torch.cat([torch.zeros((lab.shape[0], 1), dtype=torch.float32, device=dev), lab], 1).contiguous()
+        self._launch(det, off, tg, None)
+
+    def update(self, out: Sequence[torch.Tensor], targets: torch.Tensor, img_hw, shapes) -> None:
+        """process_batch for every image of a batch in one launch sequence; the arguments of DetectionMetrics.update.
+        Images without detections count their labels as missed (what process_batch does when it is given none)."""
+        B = len(out)
+        if len(shapes) != B:
+            raise ValueError(f"{len(shapes)} shapes for {B} images")
+        if B == 0:
+            return
+        dev = self.device
+        det, off = _pack(out, dev)
+        tg = targets.detach().to(dev, torch.float32).reshape(-1, 6).contiguous()
+        geom = torch.tensor([_geometry(img_hw, s) for s in shapes], dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+        self._launch(det, off, tg, geom)
+
+    def _read(self):
+        host = torch.empty(self._matrix.numel() + 2, dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.cat([self._matrix, self._info.to(torch.int64)]), non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        a = host.numpy()
+        return a[:-2].reshape(self.nc + 1, self.nc + 1), int(a[-2]), int(a[-1])
+
+    def bad_classes(self):
+        """(labels, kept detections) seen so far whose class is not an integral value in [0, nc); none of them counted."""
+        return self._read()[1:]
+
+    @property
+    def matrix(self) -> np.ndarray:
+        """The reference's attribute: numpy float64 (nc+1, nc+1).  Reads the device once."""
+        m, bad_l, bad_d = self._read()
+        if bad_l or bad_d:
+            raise ValueError(f"{bad_l} label and {bad_d} detection classes are not integral values in [0, {self.nc})")
+        return m.astype(np.float64)
+
+    def normalized(self) -> np.ndarray:
+        """The array plot() draws (metrics.py:164), before it blanks the cells below 0.005."""
+        m = self.matrix
+        return m / (m.sum(0).reshape(1, self.nc + 1) + 1E-6)
+
+    def plot(self, save_dir="", names=()):
+        raise NotImplementedError("ConfusionMatrix.plot: the heat map is not drawn; normalized() returns its array")
+
+    def print(self):
+        m = self.matrix
+        for i in range(self.nc + 1):
+            print(" ".join(map(str, m[i])))
+
+
+def output_to_target(output: Sequence[torch.Tensor]) -> torch.Tensor:
+    """plots.py:105-112 on the device: the NMS list as one (n, 7) f32 tensor [batch_id, class, x, y, w, h, conf]
+    (xyxy2xywh of general.py:259-266), without the reference's .cpu() and Python loop per box."""
+    dev = output[0].device if len(output) else _device()
+    det, _ = _pack(output, dev)
+    ids = np.repeat(np.arange(len(output), dtype=np.float32), [int(o.shape[0]) for o in output])
+    bid = torch.from_numpy(ids).pin_memory().to(dev, non_blocking=True)
+    x1, y1, x2, y2, conf, cls = det.unbind(1)
+    return torch.stack([bid, cls, (x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1, conf], 1)

@@ -540,6 +540,23 @@ def ap_per_class(tp, conf, pred_cls, target_cls, nc, ws, p, r, f1, ap, classes, 
             _p(ws), ws.numel() * ws.element_size(), _p(p), _p(r), _p(f1), _p(ap), _p(classes), _p(nt_count), _p(info))
 
 
+def confusion_workspace_bytes(B: int, n_det: int, nt: int) -> int:
+    b = C.c_size_t(0)
+    rc = _lib.sodt_confusion_update_workspace_bytes(int(B), int(n_det), int(nt), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_confusion_update_workspace_bytes failed with status {rc}")
+    return int(b.value)
+
+
+def confusion_update(det, det_off, targets, geom, nc, conf, iou_thres, ws, matrix, info):
+    """ConfusionMatrix.process_batch (metrics.py:117-155) for one batch, added into matrix ((nc+1)^2 int64) and info
+    (int32[2]).  det / det_off / targets / geom as eval_match; geom None: boxes as given, targets [img cls x1 y1 x2 y2]."""
+    B = det_off.numel() - 1
+    _launch("sodt_confusion_update", _p(det), _p(det_off), B, det.shape[0], _p(targets), targets.shape[0],
+            _p(geom), int(nc), C.c_float(conf), C.c_float(iou_thres),
+            _p(ws), ws.numel() * ws.element_size(), _p(matrix), _p(info))
+
+
 def prep_weights(table_dev, n, max_elems, dtype_code):
     _launch("sodt_prep_weights", _p(table_dev), n, max_elems, dtype_code)
 

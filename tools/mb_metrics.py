@@ -2,7 +2,13 @@
 reference-style host loop of test.py:155-262 (tests/metrics_ref.py), both on the same GPU tensors from
 R.synthetic_predictions -> non_max_suppression.  Prints one JSON line.
 
+--confusion times the confusion matrix of one batch instead: sodt_confusion_update and sodt_eval_match on the same
+packed batch by device events, ConfusionMatrix.update as a whole (events, and the host time it takes to enqueue), and
+the reference's own path (tests/confusion_ref.py host_path: box_iou on the device, one .cpu().numpy() and the numpy /
+Python matching per image) by the wall clock.
+
 usage: python tools/mb_metrics.py [--images 500] [--batch 16] [--reps 3]
+       python tools/mb_metrics.py --confusion [--batch 8] [--labels 40] [--reps 20]
 """
 from __future__ import annotations
 
@@ -21,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import ref_torch as R  # noqa: E402
 import metrics_ref as MR  # noqa: E402
+import confusion_ref as CR  # noqa: E402
 
 PKG = "small-object-detection-transformers_amd"
 
@@ -42,13 +49,100 @@ def make_batches(nms, n_images, bs, nc, dev, rng):
     return batches
 
 
+def _event_ms(fn, reps, inner=10):
+    """Median device time of one fn() by events on the current stream: reps pairs around `inner` back-to-back calls
+    (a single launch sequence is too short for one pair), after one warm-up call."""
+    fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s, e in ev:
+        s.record()
+        for _ in range(inner):
+            fn()
+        e.record()
+    torch.cuda.synchronize()
+    return float(np.median([s.elapsed_time(e) for s, e in ev])) / inner
+
+
+def confusion(a, dev):
+    nms = importlib.import_module(PKG + ".nms")
+    metrics = importlib.import_module(PKG + ".metrics")
+    ops = importlib.import_module(PKG + ".ops")
+    nc, B, img_hw = 8, a.batch, (1024, 1024)
+    rng = np.random.default_rng(0)
+    z = R.synthetic_predictions(B, 20000, nc, seed=0, img=1024.0, clusters=200).to(dev)
+    out = nms.non_max_suppression(z, 0.001, 0.6, multi_label=True)
+    tg = []
+    for b, o in enumerate(out):                       # labels: shifted copies of some detections, the rest anywhere
+        k = o[torch.from_numpy(rng.permutation(len(o))[:a.labels // 2]).to(dev)]
+        xy, wh = (k[:, :2] + k[:, 2:4]) / 2 + 1.5, k[:, 2:4] - k[:, :2]
+        n = a.labels - len(k)
+        r = torch.from_numpy(np.concatenate([rng.uniform(0, nc, (n, 1)) // 1, rng.uniform(100, 900, (n, 2)),
+                                             rng.uniform(8, 60, (n, 2))], 1).astype(np.float32)).to(dev)
+        tg.append(torch.cat([torch.full((a.labels, 1), float(b), device=dev),
+                             torch.cat([torch.cat([k[:, 5:6], xy, wh], 1), r])], 1))
+    tg = torch.cat(tg)
+    shapes = [((768, 1024), ((0.75 * 1024 / 768, 1.0), (0.0, 128.0)))] * B
+    geom = torch.tensor([MR.geometry(img_hw, s) for s in shapes], dtype=torch.float32, device=dev)
+    det, off = metrics._pack(out, dev)
+    n_det, nt = det.shape[0], tg.shape[0]
+    cm = metrics.ConfusionMatrix(nc)
+    ws_c = torch.empty(ops.confusion_workspace_bytes(B, n_det, nt), dtype=torch.uint8, device=dev)
+    ws_m = torch.empty(ops.eval_match_workspace_bytes(B, n_det, nt), dtype=torch.uint8, device=dev)
+    correct = torch.empty((n_det, 10), dtype=torch.uint8, device=dev)
+    tcls = torch.empty(nt, dtype=torch.float32, device=dev)
+    iouv = torch.linspace(0.5, 0.95, 10).tolist()
+    kernel_ms = _event_ms(lambda: ops.confusion_update(det, off, tg, geom, nc, 0.25, 0.45, ws_c, cm._matrix, cm._info), a.reps)
+    match_ms = _event_ms(lambda: ops.eval_match(det, off, tg, geom, iouv, ws_m, correct, tcls), a.reps)
+    update_ms = _event_ms(lambda: cm.update(out, tg, img_hw, shapes), a.reps)
+    enq, host = [], []
+    gl = [[float(v) for v in g] for g in geom.cpu()]
+    for _ in range(a.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cm.update(out, tg, img_hw, shapes)
+        enq.append(time.perf_counter() - t0)
+        torch.cuda.synchronize()
+        ref = np.zeros((nc + 1, nc + 1))
+        t0 = time.perf_counter()
+        for b, o in enumerate(out):                   # test.py:170 and :213-216, then process_batch, per image
+            h0, w0, gain, pw, ph = gl[b]
+            lab = tg[tg[:, 0] == b, 1:]
+
+            def scale(c):
+                c[:, [0, 2]] -= pw
+                c[:, [1, 3]] -= ph
+                c[:, :4] /= gain
+                c[:, [0, 2]] = c[:, [0, 2]].clamp(0, w0)
+                c[:, [1, 3]] = c[:, [1, 3]].clamp(0, h0)
+                return c
+            predn = scale(o.clone())
+            tbox = scale(torch.cat((lab[:, 1:3] - lab[:, 3:5] / 2, lab[:, 1:3] + lab[:, 3:5] / 2), 1))
+            CR.host_path(ref, predn, torch.cat((lab[:, 0:1], tbox), 1), nc)
+        host.append(time.perf_counter() - t0)
+    cm.reset()
+    cm.update(out, tg, img_hw, shapes)
+    got = cm.matrix
+    print(json.dumps({
+        "mode": "confusion", "batch": B, "detections": n_det, "labels": nt, "nc": nc,
+        "confusion_update_ms": round(kernel_ms, 4), "eval_match_ms": round(match_ms, 4),
+        "ratio_to_eval_match": round(kernel_ms / match_ms, 3), "update_device_ms": round(update_ms, 4),
+        "update_enqueue_ms": round(1e3 * float(np.median(enq)), 3), "host_path_ms": round(1e3 * float(np.median(host)), 2),
+        "counts": int(got.sum()), "equals_host_path": bool(np.array_equal(got, ref))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=500)
-    ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--confusion", action="store_true", help="time the confusion matrix of one batch")
+    ap.add_argument("--labels", type=int, default=40, help="--confusion: labels per image")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.confusion:
+        a.batch, a.reps = a.batch or 8, a.reps or 20
+        return confusion(a, dev)
+    a.batch, a.reps = a.batch or 16, a.reps or 3
     nms = importlib.import_module(PKG + ".nms")
     metrics = importlib.import_module(PKG + ".metrics")
     nc = 8
