@@ -548,6 +548,35 @@ int sodt_yolo_loss_fl(const float* pred, const float* targets, int nt, const flo
                       int nc, float h_box, float h_cls, float cls_pw, float h_obj, float obj_pw, float anchor_t, float gr,
                       float fl_gamma, void* ws, size_t ws_bytes, float* dpred, float* out4, sodt_stream_t st);
 
+/* The super-resolution term of the training loss under --super (csrc/srloss.hip), Train.py:420-427:
+ *   SODT_SR_IR      0.5 * L1Loss()(output_sr, ir_image)                                      C == 1, plane 0 of ir
+ *   SODT_SR_RGB     0.5 * L1Loss()(output_sr, image)                                         C == c_rgb
+ *   SODT_SR_RGB_IR  0.1 * (L1Loss()(output_sr[:, 0:3], image) + L1Loss()(output_sr[:, 3:], ir_image[:, 0:1]))
+ *                                                                                            C == 4, c_rgb == 3
+ * with image = imgs.float() / 255.0 (Train.py:364-365) formed per element from the uint8 batch, never stored.
+ * sr: output_sr, f32 (B, C, H, W) contiguous.  rgb / ir: (B, c_rgb, H, W) / (B, c_ir, H, W) contiguous, target_dtype SODT_U8
+ * (the dataloader's batches; t = float(u8) / 255.0f, bit for bit torch's) or SODT_F32 (targets already in [0, 1]); of ir
+ * (c_ir >= 1) only plane 0 of each image is read; the tensor a mode does not use may be NULL.  B * C <= 65535, H * W < 2^31.
+ * sodt_sr_l1_fwd: one pass; |o - t| in f32, the sums of the two groups (planes 0:3, plane 3; one group in the one-mode
+ *   branches) in f64 through per-block partials in ws that the last block (a ticket) adds in block order: *loss (device,
+ *   one f32) = (float)(w * (s0 / n0 + s1 / n1)), the same bits for the same inputs on every call.  ws: 16-byte aligned,
+ *   at least sodt_sr_l1_workspace_bytes(B, C, H, W); its first 16 bytes are zeroed by the entry before the launch.
+ * sodt_sr_l1_bwd: one pass; dsr (f32, like sr) = (float)(*upstream * w / n_group) * sign(o - t), sign(0) = 0, from sr and the
+ *   targets again (nothing is kept from the forward).  upstream: DEVICE pointer to one f32, the incoming gradient of the loss
+ *   (GradScaler's scale, the world size and the --quad factor of Train.py:439-445 arrive through it).
+ * Planes whose size is not a multiple of 4, or unaligned bases, run the element-wise form of the same kernels.
+ * SODT_EINVAL, nothing launched or written: a null pointer that the mode needs, a shape outside the above, C / c_rgb / c_ir
+ * that do not fit the mode, an unknown mode or target_dtype, f32 pointers off a 4-byte boundary, ws too small or unaligned. */
+#define SODT_U8 2
+#define SODT_SR_IR 0
+#define SODT_SR_RGB 1
+#define SODT_SR_RGB_IR 2
+int sodt_sr_l1_workspace_bytes(int B, int C, int H, int W, size_t* bytes);
+int sodt_sr_l1_fwd(const float* sr, const void* rgb, const void* ir, int target_dtype, int mode, int B, int C, int c_rgb,
+                   int c_ir, int H, int W, void* ws, size_t ws_bytes, float* loss, sodt_stream_t st);
+int sodt_sr_l1_bwd(const float* sr, const void* rgb, const void* ir, int target_dtype, int mode, int B, int C, int c_rgb,
+                   int c_ir, int H, int W, const float* upstream, float* dsr, sodt_stream_t st);
+
 /* hipMemsetAsync(p, 0, bytes) on the stream (statistics / gradient accumulators) */
 int sodt_memset_zero(void* p, long bytes, sodt_stream_t st);
 

@@ -24,6 +24,8 @@ def overrides():
 
 MAX_SEG = 9
 F32, BF16 = 0, 1
+U8 = 2                                                # SODT_U8: target dtype of sodt_sr_l1_fwd / _bwd
+SR_MODES = {"IR": 0, "RGB": 1, "RGB+IR": 2}           # SODT_SR_IR / SODT_SR_RGB / SODT_SR_RGB_IR
 EPI_BIAS, EPI_RESID, EPI_GELU_DUAL, EPI_DGELU = 1, 2, 4, 8
 EPI_STATS, EPI_AFFINE_SILU, EPI_DETECT, EPI_OUT_F32 = 16, 32, 64, 128
 EPI_GELU, EPI_DGELU_RC, EPI_RELU, EPI_DRELU = 256, 512, 2048, 4096      # (1024: retired, see include/sodt_hip.h)
@@ -144,6 +146,9 @@ SIGNATURES = {
     "sodt_adam_ema_step_ctl": [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _F, _P],
     "sodt_preprocess_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_sr_l1_workspace_bytes": [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    "sodt_sr_l1_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P],
+    "sodt_sr_l1_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "sodt_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_pixel_shuffle2": [_P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -9,6 +9,11 @@ and the objectness BCE in the reference's ``FocalLoss(BCEWithLogitsLoss(pos_weig
 (basics/utils/loss.py:36-62, :103-108), value and gradient, inside the same four launches (``sodt_yolo_loss_fl``);
 ``fl_gamma == 0`` calls ``sodt_yolo_loss`` as before.
 
+``SRLoss`` is the term ``--super`` adds to that loss (Train.py:420-427), computed from ``output_sr`` and the uint8 batches
+the dataloader delivers in one pass forward and one pass backward (csrc/srloss.hip, ``sodt_sr_l1_fwd`` / ``_bwd``):
+``loss += SRLoss(opt.input_mode)(output_sr, imgs_u8, irs_u8)`` replaces the three branches, and the full-resolution f32
+``image`` / ``ir_image`` of Train.py:364-365 are no longer needed for it.
+
 Not carried over: ``autobalance`` (off in Train.py:281) and label smoothing other than the reference's hard-coded
 ``smooth_BCE(eps=0.0)`` (loss.py:104); asking for them raises.
 """
@@ -94,3 +99,85 @@ class ComputeLoss:
         hyp = {k: float(self.hyp[k]) for k in ("box", "cls", "cls_pw", "obj", "obj_pw", "anchor_t")}
         hyp["fl_gamma"] = float(self.hyp.get("fl_gamma", 0.0))      # read per call, like the rest: --evolve rewrites hyp
         return _LossFn.apply(pred, targets, anchors, hyp, float(self.gr), int(self.nc))
+
+
+class _SRLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output_sr, rgb, ir, mode):
+        B, Cc, H, W = output_sr.shape
+        ws = torch.empty(ops.sr_l1_workspace_bytes(B, Cc, H, W), device=output_sr.device, dtype=torch.uint8)
+        loss = torch.empty((), device=output_sr.device, dtype=torch.float32)
+        ops.sr_l1_fwd(output_sr, rgb, ir, mode, ws, loss)
+        # references to the inputs, not copies: the backward reads output_sr and the targets again
+        ctx.save_for_backward(output_sr, rgb, ir)
+        ctx.mode = mode
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        output_sr, rgb, ir = ctx.saved_tensors
+        # the incoming gradient stays on the device: it carries GradScaler's scale, the world size and the --quad factor
+        upstream = g_loss.to(torch.float32).contiguous()
+        dsr = torch.empty_like(output_sr)
+        ops.sr_l1_bwd(output_sr, rgb, ir, ctx.mode, upstream, dsr)
+        return dsr, None, None, None
+
+
+class SRLoss:
+    """The super-resolution term of Train.py:420-427 (``--super``) for ``input_mode`` 'IR', 'RGB' or 'RGB+IR':
+
+        0.5 * L1(output_sr, ir)   |   0.5 * L1(output_sr, rgb)   |   0.1 * (L1(output_sr[:, :3], rgb) + L1(output_sr[:, 3:], ir[:, :1]))
+
+    ``SRLoss(input_mode)(output_sr, rgb, ir)`` -> 0-dim f32 device tensor with autograd.  ``output_sr``: f32 (B, C, H, W)
+    contiguous, as the engine returns it; ``rgb`` / ``ir``: the uint8 (B, c, H, W) batches as the dataloader delivers them
+    (``t = u8 / 255`` is formed per element, as ``imgs.float() / 255.0`` does), or f32 tensors already in [0, 1]; of ``ir``
+    only plane 0 is read; the batch a mode does not use may be None.  Anything else raises ValueError before a launch."""
+
+    def __init__(self, input_mode: str = "RGB+IR"):
+        if input_mode not in L.SR_MODES:
+            raise ValueError(f"SRLoss: input_mode must be one of {sorted(L.SR_MODES)}, not {input_mode!r}")
+        self.input_mode = input_mode
+
+    def _check(self, output_sr, rgb, ir):
+        mode = self.input_mode
+        if not isinstance(output_sr, torch.Tensor) or output_sr.dim() != 4:
+            raise ValueError("SRLoss: output_sr must be a (B, C, H, W) tensor")
+        if output_sr.dtype != torch.float32:
+            raise ValueError(f"SRLoss: output_sr must be float32, not {output_sr.dtype}")
+        if not output_sr.is_contiguous():
+            raise ValueError("SRLoss: output_sr must be contiguous (NCHW)")
+        B, Cc, H, W = output_sr.shape
+        if output_sr.numel() == 0 or B * Cc > 65535 or H * W >= 2 ** 31:
+            raise ValueError(f"SRLoss: unsupported output_sr shape {tuple(output_sr.shape)}")
+        want = {"IR": (1, None), "RGB": (Cc, Cc), "RGB+IR": (4, 3)}[mode]
+        if Cc != want[0]:
+            raise ValueError(f"SRLoss: input_mode {mode!r} needs output_sr with {want[0]} channel(s), got C = {Cc}")
+        used = {"IR": (("ir", ir),), "RGB": (("rgb", rgb),), "RGB+IR": (("rgb", rgb), ("ir", ir))}[mode]
+        for name, t in used:
+            if not isinstance(t, torch.Tensor) or t.dim() != 4:
+                raise ValueError(f"SRLoss: {name} must be a (B, c, H, W) tensor for input_mode {mode!r}")
+            if t.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"SRLoss: {name} must be uint8 (or float32 in [0, 1]), not {t.dtype}")
+            if t.dtype != used[0][1].dtype:
+                raise ValueError("SRLoss: rgb and ir must have the same dtype")
+            if t.shape[0] != B or tuple(t.shape[2:]) != (H, W):
+                raise ValueError(f"SRLoss: {name} has shape {tuple(t.shape)}, output_sr {tuple(output_sr.shape)}: "
+                                 "batch and spatial size must agree")
+            if name == "rgb" and t.shape[1] != want[1]:
+                raise ValueError(f"SRLoss: rgb must have {want[1]} channels for input_mode {mode!r}, got {t.shape[1]}")
+            if t.shape[1] < 1:
+                raise ValueError(f"SRLoss: {name} has no channel")
+            if not t.is_contiguous():
+                raise ValueError(f"SRLoss: {name} must be contiguous")
+        if not output_sr.is_cuda:
+            raise ValueError("SRLoss: output_sr must be on the GPU device: there is no CPU fallback")
+        for name, t in used:
+            if t.device != output_sr.device:
+                raise ValueError(f"SRLoss: {name} is on device {t.device}, output_sr on {output_sr.device}")
+        return dict(used)
+
+    def __call__(self, output_sr, rgb=None, ir=None):
+        used = self._check(output_sr, rgb, ir)
+        return _SRLossFn.apply(output_sr, used.get("rgb"), used.get("ir"), self.input_mode)

@@ -646,6 +646,33 @@ def adam_ema_step_ctl(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr
             int(bool(decoupled)), _p(ctl), C.c_float(ema_decay))
 
 
+def sr_l1_workspace_bytes(B: int, C_: int, H: int, W: int) -> int:
+    b = C.c_size_t(0)
+    rc = _lib.sodt_sr_l1_workspace_bytes(int(B), int(C_), int(H), int(W), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_sr_l1_workspace_bytes failed with status {rc} (B * C <= 65535, H * W < 2^31)")
+    return int(b.value)
+
+
+def _sr_l1_args(sr, rgb, ir, mode):
+    tgt = ir if rgb is None else rgb
+    code = L.U8 if tgt.dtype == torch.uint8 else L.F32
+    B, Cc, H, W = sr.shape
+    return (_p(sr), _p(rgb), _p(ir), code, L.SR_MODES[mode], B, Cc, 0 if rgb is None else rgb.shape[1],
+            0 if ir is None else ir.shape[1], H, W)
+
+
+def sr_l1_fwd(sr, rgb, ir, mode, ws, loss):
+    """The --super term of Train.py:420-427 in one pass (csrc/srloss.hip): sr f32 (B, C, H, W), rgb / ir uint8 (or f32 in
+    [0, 1]) batches, either None where `mode` ('IR', 'RGB', 'RGB+IR') does not use it; loss: one f32 on the device."""
+    _launch("sodt_sr_l1_fwd", *_sr_l1_args(sr, rgb, ir, mode), _p(ws), ws.numel() * ws.element_size(), _p(loss))
+
+
+def sr_l1_bwd(sr, rgb, ir, mode, upstream, dsr):
+    """dsr = upstream * w / n_group * sign(sr - target) in one pass; upstream is a one-element f32 DEVICE tensor."""
+    _launch("sodt_sr_l1_bwd", *_sr_l1_args(sr, rgb, ir, mode), _p(upstream), _p(dsr))
+
+
 def maxpool5_fwd(x, y, argmax, B, H, W, Cc, ldx=None, ldy=None, x_off=0, y_off=0):
     """y = MaxPool2d(5, 1, 2)(x), token-major; x / y may be channel slices of wider tensors (ld*, *_off in elements)."""
     es = x.element_size()

@@ -1,5 +1,11 @@
 """Time the training step of Model(sr=True) (BASELINE config 5: SRyolo_MF.yaml, super-resolution branch, batch 4 @ 2048x2048)
-next to the same step without the branch.  Usage: python tools/sr_step.py [--batch 4] [--size 2048] [--steps 5] [--dtype bf16]"""
+next to the same step without the branch.  Usage: python tools/sr_step.py [--batch 4] [--size 2048] [--steps 5] [--dtype bf16]
+
+--sr-loss picks what drives the branch (one or more values, each timed on the same model, the model without the branch is
+then skipped): `square` (the default: mean of squares, as before), `torch` (the --super term of Train.py:420-427 spelled with
+torch ops on f32 targets made per step from a uint8 batch, Train.py:364-365) or `fused` (loss.SRLoss on that uint8 batch).
+With `torch` / `fused` it also prints --windows step times, the peak memory, and the loss-plus-gradient segment alone -
+value and gradient with respect to a detached output_sr - timed with device events."""
 import argparse
 import importlib
 import os
@@ -12,42 +18,88 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def torch_sr_loss(out_sr, image, ir_image):
+    L1 = torch.nn.L1Loss()
+    return 0.1 * (L1(out_sr[:, 0:3, :, :, ], image) + L1(out_sr[:, 3:, :, :, ], ir_image[:, 0:1, :, :, ]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--size", type=int, default=2048)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--sr-loss", nargs="+", default=["square"], choices=["square", "torch", "fused"])
+    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each (torch / fused)")
     a = ap.parse_args()
     M = importlib.import_module("small-object-detection-transformers_amd.model")
+    LS = importlib.import_module("small-object-detection-transformers_amd.loss")
     dev = torch.device("cuda:0")
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     g = torch.Generator().manual_seed(0)
     x = torch.rand(a.batch, 3, a.size, a.size, generator=g).to(dev)
     ir = torch.rand(a.batch, 1, a.size, a.size, generator=g).to(dev)
-    for sr in (False, True):
+    plain = a.sr_loss == ["square"]
+    if not plain:             # the dataloader's uint8 batches at the resolution of output_sr (Train.py:362)
+        hr_u8 = torch.randint(0, 256, (a.batch, 3, 2 * a.size, 2 * a.size), generator=g, dtype=torch.uint8).to(dev)
+        ir_u8 = torch.randint(0, 256, (a.batch, 1, 2 * a.size, 2 * a.size), generator=g, dtype=torch.uint8).to(dev)
+        sr_loss = LS.SRLoss("RGB+IR")
+    for sr in ((False, True) if plain else (True,)):
         torch.manual_seed(0)
         m = M.Model("SRyolo_MF.yaml", input_mode="RGB+IR", ch_steam=3, ch=128, nc=8, sr=sr).to(dev)
         m.compute_dtype = dt
         m.train()
+        for kind in a.sr_loss:
+            def sr_term(out_sr):
+                if kind == "square":
+                    return out_sr.square().mean()
+                if kind == "fused":
+                    return sr_loss(out_sr, hr_u8, ir_u8)
+                return torch_sr_loss(out_sr, hr_u8.float() / 255.0, ir_u8.float() / 255.0)
 
-        def step():
-            out = m(x, ir, "RGB+IR")
-            loss = out[0][0].float().square().mean()
-            if sr:
-                loss = loss + out[1].square().mean()
-            loss.backward()
-        for _ in range(2):
-            step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step()
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) / a.steps * 1e3
-        print(f"sr={sr}: B={a.batch} @ {a.size}^2 {a.dtype}: {ms:.1f} ms / step, {a.batch / ms * 1e3:.1f} img/s, "
-              f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
-        del m, step
+            def step():
+                out = m(x, ir, "RGB+IR")
+                loss = out[0][0].float().square().mean()
+                if sr:
+                    loss = loss + sr_term(out[1])
+                loss.backward()
+            torch.cuda.reset_peak_memory_stats()
+            for _ in range(2):
+                step()
+            times = []
+            for _ in range(1 if kind == "square" else a.windows):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step()
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) / a.steps * 1e3)
+            ms = min(times)
+            print(f"sr={sr}{'' if plain else ' sr-loss=' + kind}: B={a.batch} @ {a.size}^2 {a.dtype}: {ms:.1f} ms / step, "
+                  f"{a.batch / ms * 1e3:.1f} img/s, peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB"
+                  + ("" if kind == "square" else f" (windows: {', '.join(f'{t:.1f}' for t in times)} ms)"), flush=True)
+            if kind != "square":
+                # the segment alone: value and gradient of the term on a detached output_sr, nothing of the model in between
+                leaf = m(x, ir, "RGB+IR")[1].detach().clone().requires_grad_(True)
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                seg = []
+                for i in range(2 + a.steps):
+                    leaf.grad = None
+                    torch.cuda.synchronize()
+                    base = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    ev[0].record()
+                    val = sr_term(leaf)
+                    val.backward()
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    if i >= 2:
+                        seg.append(ev[0].elapsed_time(ev[1]))
+                extra = (torch.cuda.max_memory_allocated() - base) / 2**30
+                print(f"  loss + gradient segment ({kind}): {min(seg):.3f} ms (median {sorted(seg)[len(seg) // 2]:.3f}), value "
+                      f"{float(val.detach()):.7f}, memory above what was held before it {extra:.2f} GiB (the gradient of output_sr included)", flush=True)
+                del leaf, val
+        del m, step, sr_term
         import gc
         gc.collect()                      # (the engine and its recorded plans refer to each other: without a collection the first model's
         torch.cuda.empty_cache()          #  46 GiB workspace is still allocated while the second one runs and lands in its "peak")
