@@ -389,6 +389,40 @@ int sodt_nms_select(const float* z, int nc, const unsigned long long* keys, long
                     int agnostic, void* ws, size_t ws_bytes, float* out, int* out_index, int* out_count,
                     sodt_stream_t st);
 
+/* ---- weighted boxes fusion (general.py:515-563, ensemble_boxes/ensemble_boxes_wbf.py), a batch per call, eval only ----
+ * sodt_wbf_candidates: general.py:523-544 for all B images in one launch.  z: (B, N, 5+nc) f32.  Keeps rows with
+ *   obj > conf_thres whose best class (first maximum of the f32 product obj * cls) has obj * cls > conf_thres, divides
+ *   cx cy w h by image_size (a true f32 division) and converts to corners in f32 (xywh2xyxy).  Per image b it writes, in
+ *   no particular order, boxes (B, N, 4) f32 [x1 y1 x2 y2] (16-byte aligned), scores (B, N) f32, labels (B, N) int32,
+ *   src (B, N) int32 = the row the candidate came from, and counts[b] (device int32) = rows of image b written.
+ * sodt_wbf_fuse: weighted_boxes_fusion (ensemble_boxes_wbf.py:150-225) for B images at once.  Image b owns rows
+ *   [b*cap, b*cap + counts[b]) of boxes (f32 corners, 16-byte aligned) / scores / labels / model / src.  model: int32
+ *   model index of each row, NULL = model 0; rows whose model is outside [0, n_models) are dropped.  src: int32 tie-break
+ *   index, NULL = the row's position.  weights: a HOST array of n_models <= 32 doubles.  conf_type: 0 avg, 1 max,
+ *   2 box_and_model_avg, 3 absent_model_aware_avg.  Rows with score < skip_box_thr (an f32 comparison) are dropped
+ *   (:31-102); the weighted score is the f64 product score * weights[model].  Within an image the rows are walked by
+ *   label, then descending weighted score, then ascending src (the reference's argsort()[::-1] leaves ties unordered).
+ *   Clustering (:183-195, find_matching_box :135-147, bb_intersection_over_union :11-28): a row joins the cluster whose
+ *   box has the greatest IoU strictly above iou_thr (f64), the earliest cluster among equal IoUs, else it starts one.
+ *   Cluster arithmetic is get_weighted_box's (:105-132): f32 coordinate sums updated as (float)((double)acc + s * x), the
+ *   score sum in f64, the fused coordinate (float)((double)acc / sum), the IoU of the f32 boxes in f64.  Confidence as
+ *   :196-218 for all four conf_type values and both allows_overflow values.  Output per image (:219-225): clusters by
+ *   descending score (ties: label, then creation order) in out_boxes (B, cap, 4) f32 (16-byte aligned), out_scores
+ *   (B, cap) f32, out_labels (B, cap) int32; out_counts[b] (device int32) = clusters of image b.  member (nullable,
+ *   (B, cap) int32): for each input row the output row of its cluster within its image, -1 for a dropped row.
+ *   scan_lanes: lanes of the workgroup that walks one (image, label) segment, 64 or 256; 0 = the default.
+ *   ws: 256-byte aligned scratch of at least sodt_wbf_fuse_workspace_bytes(B, cap) (one cluster per row at worst).
+ *   B <= 65535, B * cap <= 2^30.  No entry allocates or synchronises.  Every argument is checked before the first launch;
+ *   SODT_EINVAL is also what a failing runtime call (a memset, a rocPRIM sort) returns part-way, and only then may
+ *   earlier launches of the same call already be queued. */
+int sodt_wbf_candidates(const float* z, int B, int N, int nc, float conf_thres, float image_size, float* boxes,
+                        float* scores, int* labels, int* src, int* counts, sodt_stream_t st);
+int sodt_wbf_fuse_workspace_bytes(int B, long cap, size_t* bytes);
+int sodt_wbf_fuse(const float* boxes, const float* scores, const int* labels, const int* model, const int* src,
+                  const int* counts, int B, long cap, const double* weights, int n_models, double iou_thr,
+                  float skip_box_thr, int conf_type, int allows_overflow, int scan_lanes, void* ws, size_t ws_bytes,
+                  float* out_boxes, float* out_scores, int* out_labels, int* out_counts, int* member, sodt_stream_t st);
+
 /* ---- validation statistics (basics/test.py:155-264, basics/utils/metrics.py:18-106), eval only ----------------
  * sodt_eval_match: the per-image true-positive matching of test.py:155-240 for a whole batch at once.
  *   det: the NMS rows of all images packed, (n_det, 6) f32 [x1 y1 x2 y2 conf cls] in letterboxed-input pixels;

@@ -94,6 +94,10 @@ SIGNATURES = {
     "sodt_nms_candidates": [_P, _I, _I, C.c_float, _I, _P, _P, _I, _P, _P],
     "sodt_nms_workspace_bytes": [_L, C.POINTER(C.c_size_t)],
     "sodt_nms_select": [_P, _I, _P, _L, C.c_float, _I, _P, C.c_size_t, _P, _P, _P, _P],
+    "sodt_wbf_candidates": [_P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    "sodt_wbf_fuse_workspace_bytes": [_I, _L, C.POINTER(C.c_size_t)],
+    "sodt_wbf_fuse": [_P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_double), _I, C.c_double, _F, _I, _I, _I, _P, C.c_size_t,
+                      _P, _P, _P, _P, _P, _P],
     "sodt_eval_match_workspace_bytes": [_I, _L, _L, C.POINTER(C.c_size_t)],
     "sodt_eval_match": [_P, _P, _I, _L, _P, _L, _P, C.POINTER(C.c_float), _P, C.c_size_t, _P, _P, _P],
     "sodt_ap_per_class_workspace_bytes": [_L, _L, _I, C.POINTER(C.c_size_t)],

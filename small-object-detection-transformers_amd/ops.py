@@ -509,6 +509,32 @@ def nms_select(z_img, keys, n_total, iou_thres, agnostic, ws, out, out_index, ou
             int(bool(agnostic)), _p(ws), ws.numel() * ws.element_size(), _p(out), _p(out_index), _p(out_count))
 
 
+def wbf_candidates(z, conf_thres, image_size, boxes, scores, labels, src, counts):
+    """z (B, N, 5+nc) f32 -> per-image compact candidates + device counts (general.py:523-544)."""
+    B, N, no = z.shape
+    _launch("sodt_wbf_candidates", _p(z), B, N, no - 5, C.c_float(conf_thres), C.c_float(image_size), _p(boxes), _p(scores),
+            _p(labels), _p(src), _p(counts))
+
+
+def wbf_fuse_workspace_bytes(B: int, cap: int) -> int:
+    b = C.c_size_t(0)
+    rc = _lib.sodt_wbf_fuse_workspace_bytes(int(B), int(cap), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_wbf_fuse_workspace_bytes failed with status {rc} (B <= 65535, B * cap <= 2^30)")
+    return int(b.value)
+
+
+def wbf_fuse(boxes, scores, labels, model, src, counts, weights, iou_thr, skip_box_thr, conf_type, allows_overflow, ws,
+             out_boxes, out_scores, out_labels, out_counts, member=None, scan_lanes=0):
+    """weighted_boxes_fusion (ensemble_boxes_wbf.py:150-225) for B images: boxes (B, cap, 4), scores / labels / model / src
+    (B, cap), counts (B); weights: host floats, one per model."""
+    B, cap = scores.shape
+    w = (C.c_double * len(weights))(*[float(v) for v in weights])
+    _launch("sodt_wbf_fuse", _p(boxes), _p(scores), _p(labels), _p(model), _p(src), _p(counts), B, cap, w, len(weights),
+            C.c_double(iou_thr), C.c_float(skip_box_thr), int(conf_type), int(bool(allows_overflow)), int(scan_lanes),
+            _p(ws), ws.numel() * ws.element_size(), _p(out_boxes), _p(out_scores), _p(out_labels), _p(out_counts), _p(member))
+
+
 def eval_match_workspace_bytes(B: int, n_det: int, nt: int) -> int:
     b = C.c_size_t(0)
     rc = _lib.sodt_eval_match_workspace_bytes(int(B), int(n_det), int(nt), C.byref(b))
