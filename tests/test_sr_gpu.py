@@ -1,7 +1,8 @@
 """The super-resolution branch on the HIP kernels (sr.py: Decoder + EDSR = DeepLab, basics/models/deeplabedsr.py:35-73,
 sr_decoder_noBN_noD.py:6-45, edsr.py:55-102) against tests/golden/sr.pt, which holds what the reference's own classes produce on the
 procedural weights (oracle/gen_golden.py --only-sr): outputs, input gradients, every parameter's gradient norm and 64 strided gradient
-values.  f32 is the parity run (tight); bf16 is the throughput dtype (loose)."""
+values.  f32 is the parity run (tight); bf16 is the throughput dtype (loose).
+The layout converters behind the _rows / _nchw helpers are pinned bit for bit by tests/test_sr_movement_gpu.py."""
 import importlib
 import os
 
