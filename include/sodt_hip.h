@@ -569,6 +569,7 @@ int sodt_preprocess_u8(const unsigned char* rgb, const unsigned char* ir, float*
  * anchors f32 (na, 2) in grid units (Detect.anchors[0]); hyper-parameters as in models/hyp.scratch.yaml (box, cls,
  * cls_pw, obj, obj_pw, anchor_t) and model.gr.  dpred f32 like pred; out4 = (loss * B, lbox, lobj, lcls) as loss.py:163.
  * Duplicate cells take the objectness target of the LAST matching candidate in the reference's order (CPU index_put).
+ * Rows whose image index is outside [0, B) are skipped: the kernel skips such rows where the reference would raise.
  * ws: scratch of sodt_yolo_loss_workspace_bytes(B*na*ny*nx, nt, nc) bytes.  nc <= 32, na <= 8. */
 int sodt_yolo_loss_workspace_bytes(long ncells, int nt, int nc, size_t* bytes);
 int sodt_yolo_loss(const float* pred, const float* targets, int nt, const float* anchors, int B, int na, int ny, int nx,
