@@ -612,6 +612,42 @@ int sodt_sr_l1_fwd(const float* sr, const void* rgb, const void* ir, int target_
 int sodt_sr_l1_bwd(const float* sr, const void* rgb, const void* ir, int target_dtype, int mode, int B, int C, int c_rgb,
                    int c_ir, int H, int W, const float* upstream, float* dsr, sodt_stream_t st);
 
+/* ---- autoanchor (basics/utils/autoanchor.py: check_anchors :24-60, kmean_anchors :63-158), start-up only (csrc/autoanchor.hip) ----
+ * wh: (N, 2) f32 label sizes in pixels (8-byte aligned), finite and positive.  An anchor set is (n, 2) f32, 1 <= n <= 32.
+ * The ratio metric of :33-35 / :80-84 per label, in f32 with IEEE division: r = wh / k, x = min over the two axes of
+ * min(r, 1 / r), best = max over the anchors of x.  thr is the threshold ALREADY inverted (1 / anchor_t) and rounded to
+ * f32, compared strictly in f32 - the rule of torch's `float32_tensor > python_float`.  Sums are f64 and counts int64,
+ * reduced per block and added by the last block in block order: equal inputs give equal bits on every call.
+ * sodt_anchor_stats: `metric` (:33-39, :80-84), `anchor_fitness` (:86-88) and every figure of `print_results` (:90-96) for
+ *   S anchor sets (S, n, 2) at once.  out: (S, 6) f64 per set: sum(best), sum(best [best > thr]), count(best > thr),
+ *   count(x > thr) over all N * n, sum(x), sum(x [x > thr]).  bpr = out[2] / N, aat = out[3] / N, fitness = out[1] / N.
+ *   N == 0 writes zeros.  S <= 65535.  ws: 16-byte aligned, at least sodt_anchor_stats_workspace_bytes(N, S).
+ * sodt_anchor_evolve: the G generations of :146-153 without a host read.  k: (n, 2) f64 and f: one f64, both DEVICE, in
+ *   and out; v: (G, n, 2) f64 DEVICE, the mutation factors of :147-149 (they depend on the random stream only).  For
+ *   g = 0 .. G-1 in order, one launch each: kg = max(k * v[g], 2.0) in f64; fg = sum(best [best > thr]) / N of float32(kg),
+ *   the sum and the mean in f64; if fg > f (f64) then f, k = fg, kg.  accepted: nullable (G) int32, 1 where generation g
+ *   was taken.  G == 0 launches nothing.  N >= 1.  ws: at least sodt_anchor_evolve_workspace_bytes(N).
+ * sodt_kmeans_lloyd: `iters` iterations of the loop inside scipy.cluster.vq.kmeans (:123) for R restarts at once, all in
+ *   f64.  obs: (N, 2) whitened points (16-byte aligned), N >= 1.  books: (R, n, 2), in and out; alive: (R, n) int32, 1 = the
+ *   centre is live; prev: (R) the last mean distortion (the caller starts it at +inf); done: (R) int32.  One iteration of a
+ *   restart that is not done: every point goes to its nearest live centre by dx*dx + dy*dy (not contracted; ties to the
+ *   lowest live index), cur = mean of the square roots, every live centre moves to the mean of its members, one without
+ *   members is marked dead (its book row is left as it is and its slot kept, so the order of the others stays),
+ *   diff = |prev - cur|, prev = cur, done = diff <= thresh - so the book is moved once more after the last distortion,
+ *   as scipy does.  A restart whose done is set is not touched again.  R <= 65535.
+ *   ws: at least sodt_kmeans_lloyd_workspace_bytes(N, R, n).
+ * SODT_EINVAL, nothing launched or written: n outside 1..32, a null or misaligned pointer, N / S / R / G / iters outside the
+ * above, a NaN threshold, ws too small.  No entry allocates or synchronises. */
+int sodt_anchor_stats_workspace_bytes(long N, int S, size_t* bytes);
+int sodt_anchor_stats(const float* wh, long N, const float* sets, int S, int n, float thr, void* ws, size_t ws_bytes,
+                      double* out, sodt_stream_t st);
+int sodt_anchor_evolve_workspace_bytes(long N, size_t* bytes);
+int sodt_anchor_evolve(const float* wh, long N, float thr, double* k, int n, double* f, const double* v, int G,
+                       int* accepted, void* ws, size_t ws_bytes, sodt_stream_t st);
+int sodt_kmeans_lloyd_workspace_bytes(long N, int R, int n, size_t* bytes);
+int sodt_kmeans_lloyd(const double* obs, long N, double* books, int* alive, double* prev, int* done, int R, int n,
+                      double thresh, int iters, void* ws, size_t ws_bytes, sodt_stream_t st);
+
 /* hipMemsetAsync(p, 0, bytes) on the stream (statistics / gradient accumulators) */
 int sodt_memset_zero(void* p, long bytes, sodt_stream_t st);
 

@@ -153,6 +153,12 @@ SIGNATURES = {
     "sodt_sr_l1_workspace_bytes": [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     "sodt_sr_l1_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P],
     "sodt_sr_l1_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "sodt_anchor_stats_workspace_bytes": [_L, _I, C.POINTER(C.c_size_t)],
+    "sodt_anchor_stats": [_P, _L, _P, _I, _I, _F, _P, C.c_size_t, _P],
+    "sodt_anchor_evolve_workspace_bytes": [_L, C.POINTER(C.c_size_t)],
+    "sodt_anchor_evolve": [_P, _L, _F, _P, _I, _P, _P, _I, _P, _P, C.c_size_t],
+    "sodt_kmeans_lloyd_workspace_bytes": [_L, _I, _I, C.POINTER(C.c_size_t)],
+    "sodt_kmeans_lloyd": [_P, _L, _P, _P, _P, _P, _I, _I, C.c_double, _I, _P, C.c_size_t],
     "sodt_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_pixel_shuffle2": [_P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -699,6 +699,49 @@ def sr_l1_bwd(sr, rgb, ir, mode, upstream, dsr):
     _launch("sodt_sr_l1_bwd", *_sr_l1_args(sr, rgb, ir, mode), _p(upstream), _p(dsr))
 
 
+def _ws_bytes(name: str, *args) -> int:
+    b = C.c_size_t(0)
+    rc = getattr(_lib, name)(*args, C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed with status {rc} (see include/sodt_hip.h)")
+    return int(b.value)
+
+
+def anchor_stats_workspace_bytes(N: int, S: int) -> int:
+    return _ws_bytes("sodt_anchor_stats_workspace_bytes", int(N), int(S))
+
+
+def anchor_stats(wh, sets, thr_inv, ws, out):
+    """autoanchor.py:33-39, :80-96 for S anchor sets: wh (N, 2) f32, sets (S, n, 2) f32, thr_inv = 1 / anchor_t (rounded to f32
+    here); out (S, 6) f64 = sum(best), sum(best [best > thr]), count(best > thr), count(x > thr), sum(x), sum(x [x > thr])."""
+    S, n, _ = sets.shape
+    _launch("sodt_anchor_stats", _p(wh), wh.shape[0], _p(sets), S, n, C.c_float(thr_inv), _p(ws),
+            ws.numel() * ws.element_size(), _p(out))
+
+
+def anchor_evolve_workspace_bytes(N: int) -> int:
+    return _ws_bytes("sodt_anchor_evolve_workspace_bytes", int(N))
+
+
+def anchor_evolve(wh, thr_inv, k, f, v, accepted, ws):
+    """autoanchor.py:146-153 for the G = v.shape[0] generations, one launch each and no host read: k (n, 2) f64 and f (1) f64
+    in and out, v (G, n, 2) f64, accepted (G) int32 or None - all on the device."""
+    _launch("sodt_anchor_evolve", _p(wh), wh.shape[0], C.c_float(thr_inv), _p(k), k.shape[0], _p(f), _p(v), v.shape[0],
+            _p(accepted), _p(ws), ws.numel() * ws.element_size())
+
+
+def kmeans_lloyd_workspace_bytes(N: int, R: int, n: int) -> int:
+    return _ws_bytes("sodt_kmeans_lloyd_workspace_bytes", int(N), int(R), int(n))
+
+
+def kmeans_lloyd(obs, books, alive, prev, done, thresh, iters, ws):
+    """`iters` iterations of the loop inside scipy.cluster.vq.kmeans for the R = books.shape[0] restarts: obs (N, 2) f64,
+    books (R, n, 2) f64, alive (R, n) int32, prev (R) f64, done (R) int32, all on the device and updated in place."""
+    R, n, _ = books.shape
+    _launch("sodt_kmeans_lloyd", _p(obs), obs.shape[0], _p(books), _p(alive), _p(prev), _p(done), R, n, C.c_double(thresh),
+            int(iters), _p(ws), ws.numel() * ws.element_size())
+
+
 def maxpool5_fwd(x, y, argmax, B, H, W, Cc, ldx=None, ldy=None, x_off=0, y_off=0):
     """y = MaxPool2d(5, 1, 2)(x), token-major; x / y may be channel slices of wider tensors (ld*, *_off in elements)."""
     es = x.element_size()
