@@ -116,6 +116,33 @@ typedef struct {
  * reference ops listed above). */
 int sodt_gemm_tn(const sodt_gemm_tn_args* g, int dtype, sodt_stream_t st);
 
+/* Backward of a square 192 -> 192 nn.Linear in one pass over dY (csrc/linbwd.hip; autograd of backbone_vit.py:990 attn.proj and
+ * :886-904 the conv-MLP's fc2), bf16 only:
+ *   dX[M][192]   = epi(dY[M][192] @ W)      W given as wT [192][192] with wT[k][n] = W[n][k] - the [N][K] operand sodt_gemm_nt takes
+ *   dW[192][192] (f32) += dY^T @ X[M][192]
+ *   dbias[192]   (f32) += column sums of dY (NULL: skipped)
+ * flags: 0, or SODT_EPI_DGELU: dX = (dY W) * gelu'(aux[m][k]) with the gelu' of sodt_gemm_nt's SODT_EPI_DGELU.
+ * dY, X, aux, dX, wT: row-major bf16, 16-byte aligned, each leading dimension a multiple of 8 elements and >= 192; dW 16-byte aligned,
+ * lddw a multiple of 4.  splits / partial / partial_floats: as in sodt_gemm_tn_args (M is cut into `splits` slices, one workgroup
+ * each; with a scratch of >= splits*N*K floats the slices' partial tiles are summed in a fixed order - run-to-run deterministic -
+ * otherwise dW gets f32 atomics; dbias goes through the scratch too when it has splits*N further floats).
+ * N or K other than 192, float32, any other flag or alignment: SODT_EINVAL, nothing written (callers run sodt_gemm_tn + sodt_gemm_nt). */
+typedef struct {
+  const void* dY; int ldy;
+  const void* X; int ldx;
+  const void* wT; int ldw;
+  const void* aux; int ldaux;
+  void* dX; int lddx;
+  float* dW; int lddw;
+  float* dbias;
+  int M, N, K, flags;
+  int splits;
+  float* partial;
+  long partial_floats;
+} sodt_linbwd_args;
+
+int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_stream_t st);
+
 /* LayerNorm over the last dim, eps 1e-5 (backbone_vit.py:1090,1128,858).  y and stats
  * (mean, rstd per row, f32 [M][2]) are written; C % (16 bytes) == 0. */
 int sodt_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,

@@ -67,6 +67,20 @@ class GemmTnArgs(C.Structure):
                 ("partial", C.c_void_p), ("partial_floats", C.c_long)]
 
 
+class LinBwdArgs(C.Structure):
+    """sodt_linbwd_args (include/sodt_hip.h): the square 192 -> 192 linear backward, dX and dW from one read of dY."""
+    _fields_ = [("dY", C.c_void_p), ("ldy", C.c_int),
+                ("X", C.c_void_p), ("ldx", C.c_int),
+                ("wT", C.c_void_p), ("ldw", C.c_int),
+                ("aux", C.c_void_p), ("ldaux", C.c_int),
+                ("dX", C.c_void_p), ("lddx", C.c_int),
+                ("dW", C.c_void_p), ("lddw", C.c_int),
+                ("dbias", C.c_void_p),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("flags", C.c_int),
+                ("splits", C.c_int),
+                ("partial", C.c_void_p), ("partial_floats", C.c_long)]
+
+
 class StepCtl(C.Structure):
     """sodt_step_ctl (include/sodt_hip.h): the 64-byte device record sodt_grad_stats fills and the _ctl steps read."""
     _fields_ = [("acc_sumsq", C.c_double), ("acc_found", C.c_uint), ("ticket", C.c_uint),
@@ -106,6 +120,7 @@ SIGNATURES = {
     "sodt_confusion_update": [_P, _P, _I, _L, _P, _L, _P, _I, _F, _F, _P, C.c_size_t, _P, _P, _P],
     "sodt_gemm_nt": [C.POINTER(GemmArgs), _I, _P],
     "sodt_gemm_tn": [C.POINTER(GemmTnArgs), _I, _P],
+    "sodt_linear_bwd_sq": [C.POINTER(LinBwdArgs), _I, _P],
     "sodt_layernorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sodt_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sodt_window_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

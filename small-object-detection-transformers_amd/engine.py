@@ -176,6 +176,9 @@ class Engine:
         self.ddp = None     # set by ddp.attach()
         self.use_fused_wmsa = True     # tests / tools may switch the fused block kernel off to compare with the four launches it replaces
         self.use_fused_mlp = True      # the same for the fused linear MLP (csrc/mlp.hip) against its two GEMM launches
+        # bf16, C = 192: backward of attn.proj and of the conv-MLP's fc2 as ONE launch each (csrc/linbwd.hip: dX and dW from one read
+        # of dY) against the sodt_gemm_tn + sodt_gemm_nt pair
+        self.use_fused_linbwd = True
         # 2x2-conv MLPs (bf16): fc1 folded into the convolution's weights (csrc/convmlp.hip) - no fc1 GEMM, and in the backward no
         # d(x) = du W1 and no dW1 GEMM; widths above this run the three-GEMM form (the composition kernels are plain f32 loops)
         self.convmlp_fold_maxc = 384
@@ -811,6 +814,8 @@ class Engine:
         xm, xn2, xn1, ao = b[tag + ".xm"], b[tag + ".xn2"], b[tag + ".xn1"], b[tag + ".ao"]
         dxn = plan.buf(f"g.dxn.{Cc}", (M, Cc))
         dxm = plan.buf(f"g.dxm.{Cc}", (M, Cc))
+        # (ops.linear_bwd_sq returns False where the entry point refuses the layer: the two launches run instead)
+        linbwd = self.use_fused_linbwd and not sv.get("pad") and plan.dt == torch.bfloat16 and Cc == 192
         if blk.mlp.linear:
             ha = b[tag + ".ha"]
             dh = plan.buf(f"g.dh.{Cc}", (M, 4 * Cc))
@@ -826,8 +831,10 @@ class Engine:
             cm = P["cmlp"][pre]
             cp, ca = b[tag + ".cp"], b[tag + ".ca"]
             dc = plan.buf(f"g.dc.{Cc}", (M, Cc))
-            ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
-            ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
+            if not (linbwd and ops.linear_bwd_sq(dY, ca, wT[pre + "mlp.fc2.weight"], dc, g[pre + "mlp.fc2.weight"], M,
+                                                 dbias=g[pre + "mlp.fc2.bias"], dgelu_aux=cp)):
+                ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
+                ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
             # d(Weff) = dc^T xn2(taps) (+ the column sums of dc), then the parameter gradients of fc1 / conv1 by the chain rule
             scr = plan.buf(f"g.cmlp.{Cc}", (Cc * 4 * Cc + 4 * Cc,), torch.float32)
             dweff, colsum, bs = scr[: Cc * 4 * Cc].view(Cc, 4 * Cc), scr[Cc * 4 * Cc: Cc * 4 * Cc + Cc], scr[Cc * 4 * Cc + Cc:].view(3, Cc)
@@ -842,8 +849,10 @@ class Engine:
             u, cp, ca = b[tag + ".u"], b[tag + ".cp"], b[tag + ".ca"]
             dc = plan.buf(f"g.dc.{Cc}", (M, Cc))
             du = plan.buf(f"g.du.{Cc}", (M, Cc))
-            ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
-            ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
+            if not (linbwd and ops.linear_bwd_sq(dY, ca, wT[pre + "mlp.fc2.weight"], dc, g[pre + "mlp.fc2.weight"], M,
+                                                 dbias=g[pre + "mlp.fc2.bias"], dgelu_aux=cp)):
+                ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
+                ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
             segs = [SegSpec(u, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
             ops.gemm_tn(dc, segs, g[pre + "mlp.conv1.weight"], M, Cc, 4 * Cc, spatial=(H, W), dbias=g[pre + "mlp.conv1.bias"],
                         kperm=(Cc, 4))
@@ -865,9 +874,11 @@ class Engine:
         if sv.get("pad"):
             self._padded_attn_bwd(plan, P, tag, pre, sv, dxm, dxn, dX)
             return
-        ops.gemm_tn(dxm, [SegSpec(ao)], g[pre + "attn.proj.weight"], M, Cc, Cc, dbias=g[pre + "attn.proj.bias"])
         dao = dxn
-        ops.gemm_nt([SegSpec(dxm)], wT[pre + "attn.proj.weight"], dao, M, Cc, Cc)
+        if not (linbwd and ops.linear_bwd_sq(dxm, ao, wT[pre + "attn.proj.weight"], dao, g[pre + "attn.proj.weight"], M,
+                                             dbias=g[pre + "attn.proj.bias"])):
+            ops.gemm_tn(dxm, [SegSpec(ao)], g[pre + "attn.proj.weight"], M, Cc, Cc, dbias=g[pre + "attn.proj.bias"])
+            ops.gemm_nt([SegSpec(dxm)], wT[pre + "attn.proj.weight"], dao, M, Cc, Cc)
         dqkv = plan.buf(f"g.dqkv.{Cc}", (M, 3 * Cc))
         L2 = 2 * ws - 1
         dbt = plan.buf(f"g.dbt.{L2}", (HEADS, L2 * L2), torch.float32, zero=True)

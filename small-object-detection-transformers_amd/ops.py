@@ -281,6 +281,51 @@ def gemm_tn(dY: torch.Tensor, segs: Sequence[SegSpec], dW: torch.Tensor, M: int,
     _launch("sodt_gemm_tn", C.byref(g), dt_code(dY))
 
 
+def linear_bwd_sq(dY: torch.Tensor, X: torch.Tensor, wT: torch.Tensor, dX: torch.Tensor, dW: torch.Tensor, M: int, *,
+                  dbias: Optional[torch.Tensor] = None, dgelu_aux: Optional[torch.Tensor] = None,
+                  ldy: Optional[int] = None, y_off: int = 0, ldx: Optional[int] = None, lddx: Optional[int] = None,
+                  lddw: Optional[int] = None, splits: Optional[int] = None) -> bool:
+    """dX[M][192] = (dY @ W) [* gelu'(dgelu_aux)], dW[192][192] (f32) += dY^T @ X, dbias += column sums of dY, from ONE read of dY;
+    wT is the [N][K] operand gemm_nt takes for the same dX.  One workgroup per M-slice, at least 16 stages of 32 rows each.
+    Returns False, with nothing launched, written or recorded, when sodt_linear_bwd_sq does not take the layer (anything but bf16
+    at 192 -> 192, a leading dimension or an address off its alignment: SODT_EINVAL): the caller then runs gemm_tn + gemm_nt."""
+    ts = [dY, X, wT, dX] + ([dgelu_aux] if dgelu_aux is not None else [])
+    if any(t.dtype != torch.bfloat16 for t in ts) or dW.dtype != torch.float32 or (dbias is not None and dbias.dtype != torch.float32):
+        return False
+    if tuple(wT.shape) != (192, 192) or X.shape[-1] < 192 or dX.shape[-1] < 192:
+        return False
+    g = L.LinBwdArgs()
+    g.dY = dY.data_ptr() + y_off * dY.element_size()
+    g.ldy = dY.shape[-1] if ldy is None else ldy
+    g.X, g.ldx = X.data_ptr(), (X.shape[-1] if ldx is None else ldx)
+    g.wT, g.ldw = wT.data_ptr(), wT.stride(0)
+    g.dX, g.lddx = dX.data_ptr(), (dX.shape[-1] if lddx is None else lddx)
+    g.dW, g.lddw = dW.data_ptr(), (192 if lddw is None else lddw)
+    g.dbias = _p(dbias)
+    g.M, g.N, g.K = M, 192, 192
+    if dgelu_aux is not None:
+        g.flags = L.EPI_DGELU
+        g.aux, g.ldaux = dgelu_aux.data_ptr(), dgelu_aux.shape[-1]
+    g.splits = linear_bwd_sq_splits(M) if splits is None else splits
+    if _tn_scratch is not None and _tn_scratch.device == dY.device and g.splits > 1:
+        g.partial, g.partial_floats = _tn_scratch.data_ptr(), _tn_scratch.numel()
+    fn = _lib.sodt_linear_bwd_sq
+    args = (C.byref(g), L.BF16)
+    rc = fn(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc == 1:                     # SODT_EINVAL: validated before any launch
+        return False
+    if rc != 0:
+        raise RuntimeError(f"sodt_linear_bwd_sq failed with status {rc}")
+    if _active_recorder is not None:
+        _active_recorder.append((fn, args, "sodt_linear_bwd_sq", _tag))
+    return True
+
+
+def linear_bwd_sq_splits(M: int) -> int:
+    """M-slices of sodt_linear_bwd_sq: one workgroup per CU, at least 16 stages of 32 rows per slice."""
+    return max(1, min(M // 512, 256))
+
+
 def layernorm_fwd(x, gamma, beta, y, stats, M, Cc):
     _launch("sodt_layernorm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), M, Cc, dt_code(x))
 

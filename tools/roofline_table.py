@@ -50,6 +50,12 @@ def cost(name, args):
             seen.add(s.p)
             kin += s.klen
         return (f"M={g.M} N={g.N} K={g.K} dW", g.M * (kin + g.N) * ES + 2.0 * g.N * g.K * 4, 2.0 * g.M * g.N * g.K)
+    if name == "sodt_linear_bwd_sq":
+        g = unwrap(args[0])
+        # dY, X in, dX out (+ aux in with SODT_EPI_DGELU): 3 or 4 passes; one partial dW tile per slice written and read, dW itself
+        npass = 4 if g.flags & 8 else 3
+        return (f"M={g.M} N={g.N} K={g.K} dX+dW{' dgelu' if g.flags & 8 else ''}",
+                g.M * npass * g.N * ES + (2.0 * g.splits + 2) * g.N * g.K * 4 + g.N * g.K * ES, 4.0 * g.M * g.N * g.K)
     if name == "sodt_wmsa_block_fwd":
         B, H, W, C = (val(args[i]) for i in (10, 11, 12, 13))
         T = B * H * W
