@@ -15,20 +15,18 @@ from __future__ import annotations
 import os
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
-
-import warnings
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib as L
 from . import ops
-from .ops import SegSpec
+from .headgraph import Ref, parse_head
+from .ops import TAPS3, SegSpec
 
 HEADS = 12
 E = "image_encoder."
 TAPS2 = ((0, 0), (0, 1), (1, 0), (1, 1))                       # (dy, dx) of the 2x2 conv, kernel index kh*2+kw
-TAPS3 = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))
 MERGE = ((0, 0), (1, 0), (0, 1), (1, 1))                        # PatchMerging gather order (backbone_vit.py:850-853)
 USE_HIPGRAPH = os.environ.get("SODT_HIPGRAPH", "0") == "1"     # opt-in: see Engine._replay
 
@@ -43,13 +41,24 @@ class Plan:
         self.fwd_pre: Optional[list] = None
         self.fwd_main: Optional[list] = None
         self.bwd_main: Optional[list] = None
-        self.saved: dict = {}
+        self.saved: dict = {}                     # tag -> BlockRoute / ConvRoute / dict: what the forward chose, for the backward
         self.graphs: dict = {}                    # hipGraph of a recorded list (captured on its first replay)
+        self.zused: Dict[str, int] = {}           # bytes handed out of each zero pool (zbuf)
+        self.sr = None                            # this plan's sr.SRBranch (Engine._sr_forward)
+        self.enc_bwd_start: Optional[int] = None  # index in bwd_main where the head's backward ends and the encoder's begins
+        self.enc_gin: Optional[list] = None       # [(buf, ld, off, c)]: where the head leaves d(f0), d(f1), d(f2)
+
+    def _cached(self, name, shape, dtype):
+        """the buffer already allocated under `name`, or None; a hit with another shape or dtype is a bug of the caller"""
+        t = self.bufs.get(name)
+        if t is not None and (tuple(t.shape) != tuple(shape) or t.dtype != dtype):
+            raise RuntimeError(f"plan buffer {name!r} is {tuple(t.shape)} {t.dtype}, requested as {tuple(shape)} {dtype}")
+        return t
 
     def zbuf(self, pool, name, shape, dtype):
         """Small accumulator that must be zero at the start of every forward (pool "f") or backward (pool "b"): carved out of
         one 2 MiB pool per direction that a single memset clears (24 tiny memset launches per step otherwise)."""
-        t = self.bufs.get(name)
+        t = self._cached(name, shape, dtype)
         if t is None:
             pbuf = self.zpool(pool)
             n = 1
@@ -68,17 +77,50 @@ class Plan:
         pbuf = self.bufs.get("zpool." + pool)
         if pbuf is None:
             pbuf = self.bufs["zpool." + pool] = torch.zeros(1 << 21, device=self.dev, dtype=torch.uint8)
-            self.zused = getattr(self, "zused", {})
             self.zused[pool] = 0
         return pbuf
 
     def buf(self, name, shape, dtype=None, zero=False):
-        t = self.bufs.get(name)
+        dtype = self.dt if dtype is None else dtype
+        t = self._cached(name, shape, dtype)
         if t is None:
-            dtype = self.dt if dtype is None else dtype
             t = (torch.zeros if zero else torch.empty)(shape, device=self.dev, dtype=dtype)
             self.bufs[name] = t
         return t
+
+    def scratch(self, kind, shape, dtype=None, zero=False):
+        """Backward scratch that every user of the same kind AND shape shares (one block's backward runs at a time)."""
+        return self.buf(f"g.{kind}.{'x'.join(str(d) for d in shape)}", shape, dtype, zero)
+
+
+# what _block_route chooses among (BlockRoute.attn / .mlp)
+ATTN_FUSED_RC, ATTN_FUSED_SAVED, ATTN_PADDED, ATTN_PLAIN = "fused, q/k/v recomputed", "fused, q/k/v saved", "padded", "plain"
+MLP_FUSED, MLP_LIN_RC, MLP_LIN_SAVED, MLP_FOLD, MLP_CONV = "fused linear", "linear, activation saved", "linear, pre-activation saved", \
+    "folded conv", "three-GEMM conv"
+
+
+class BlockRoute(NamedTuple):
+    """Everything one Swin block's forward chose (_block_route): the backward selects its launches from this alone."""
+    x_in: torch.Tensor
+    geo: tuple                          # (B, H, W, C, ws, shift)
+    pad: Optional[Tuple[int, int]]      # the padded grid (Hp, Wp) of a resolution that is no multiple of the window
+    attn: str                           # ATTN_*
+    wpk: Optional[torch.Tensor]         # parameter pack of the fused W-MSA kernel
+    mlp: str                            # MLP_*
+    zscratch: bool                      # window above 64 tokens: the five-launch attention backward needs its zeroed scratch
+    sq_ok: bool                         # attn.proj / fc2 backward may take the square one-launch form (use_fused_linbwd permitting)
+
+
+class ConvRoute(NamedTuple):
+    """One head Conv2d+BN+SiLU as _conv_fwd ran it."""
+    segs: list
+    spatial: Optional[Tuple[int, int]]
+    M: int
+    K: int
+    Cout: int
+    k: int
+    pname: str
+    direct: bool                        # the 3x3 at 64 -> 64 channels on the direct kernels (csrc/conv3.hip)
 
 
 class _LazyFeatures(list):
@@ -164,7 +206,8 @@ class Engine:
         self.det_np = (det.na * det.no + 15) // 16 * 16      # Detect GEMM width, zero-padded to a multiple of 16 (39 -> 48 at nc = 8)
         self.fused = not any(type(m).__name__ == "BatchNorm2d" for m in model.detect.modules())
         self.sr = bool(getattr(model, "sr", False))
-        self._check_head()
+        self.head = parse_head(model)             # headgraph.HeadGraph: units, Upsample / Concat rules, Detect's input, SR taps
+        self.det_name = f"detect.{self.head.nd}."
         self.plans: Dict[Tuple, Plan] = {}
         self.probes_fwd: Optional[dict] = None    # bench.py: {call index: (start event, end event)}
         self.probes_bwd: Optional[dict] = None
@@ -186,111 +229,6 @@ class Engine:
         # 64 MiB of f32 for the per-slice partial tiles of the bf16 weight-gradient GEMMs (largest need: 12.5 M floats)
         self._tn_scratch = torch.empty(16 << 20, dtype=torch.float32, device=self.dev)
         ops.set_tn_scratch(self._tn_scratch)
-
-    # ------------------------------------------------------------------ head graph
-    def _check_head(self):
-        """Parse ``model.detect`` (parse_model's nn.Sequential with the reference's ``.f`` wiring, model.py:268-281) into a
-        launch plan.  Accepted: any CHAIN of compute units - Conv (1x1 or 3x3, stride 1), C3 (n = 1), SPP - in which every
-        unit reads ONE feature-list entry, possibly through nn.Upsample(x2, nearest) and Concat rows (their inputs: the
-        previous rows or encoder outputs y[0..2]), ending in a one-layer Detect; every unit output and every encoder output
-        is consumed exactly once.  That covers models/model.yaml:65-74, the identical head of SRyolo_MF.yaml:52-71, and
-        variants with extra Conv / SPP (common.py:129-140) rows.  Upsample and Concat never move data: they become the
-        K-segments (source + spatial map) of the consuming unit's first GEMM."""
-        from . import model as M
-        d = self.model.detect
-        enc_c = (256, 256, 512)                                   # neck widths (backbone_vit.py:167-187), levels 0, 1, 2
-        # virtual tensor: (parts, level) with parts = [(ref, C, shr)], ref = ("enc", j) | ("unit", k); resolution t >> level
-        vals = {j: ([(("enc", j), enc_c[j], 0)], j) for j in range(3)}
-        units, rules = [], {}
-        uses: Dict[tuple, int] = {}
-
-        def resolve(f, yi):
-            j = yi - 1 if f == -1 else f
-            if not isinstance(j, int) or j not in vals or j >= yi:
-                raise NotImplementedError(f"head row {yi - 3}: input {f!r} does not name an earlier feature-list entry")
-            return j
-        if not isinstance(d[-1], M.Detect) or d[-1].nl != 1:
-            raise NotImplementedError("the head must end in a one-layer Detect (models/model.yaml:74)")
-        for k, m in enumerate(d):
-            yi, kind = 3 + k, type(m).__name__
-            if kind in ("Conv", "C3", "SPP"):
-                if not isinstance(m.f, int):
-                    raise NotImplementedError(f"head row {k}: {kind} takes one input")
-                parts, level = vals[resolve(m.f, yi)]
-                c1 = sum(c for _, c, _ in parts)
-                if kind == "Conv":
-                    kk, c2 = m.conv.kernel_size[0], m.conv.out_channels
-                    if m.conv.in_channels != c1:
-                        raise NotImplementedError(f"head row {k}: Conv expects {m.conv.in_channels} channels, graph gives {c1}")
-                    if kk == 3 and len(parts) * 9 > L.MAX_SEG:
-                        raise NotImplementedError(f"head row {k}: a 3x3 Conv on a concatenation needs {len(parts) * 9} K-segments (max {L.MAX_SEG})")
-                elif kind == "C3":
-                    kk, c2 = 1, m.cv3.conv.out_channels
-                    if len(m.m) != 1 or m.m[0].add:
-                        raise NotImplementedError("C3 with n=1, shortcut=False only (models/model.yaml:68,73)")
-                    if m.cv1.conv.in_channels != c1:
-                        raise NotImplementedError(f"head row {k}: C3 expects {m.cv1.conv.in_channels} channels, graph gives {c1}")
-                else:
-                    kk, c2 = 1, m.cv2.conv.out_channels
-                    if m.cv1.conv.in_channels != c1:
-                        raise NotImplementedError(f"head row {k}: SPP expects {m.cv1.conv.in_channels} channels, graph gives {c1}")
-                for ref, _, _ in parts:
-                    uses[ref] = uses.get(ref, 0) + 1
-                units.append(dict(k=k, kind=kind, parts=parts, level=level, c1=c1, c2=c2, ksize=kk))
-                vals[yi] = ([(("unit", k), c2, 0)], level)
-            elif kind == "Upsample":
-                parts, level = vals[resolve(m.f, yi)]
-                if level == 0:
-                    raise NotImplementedError(f"head row {k}: Upsample above the stride-4 grid of Detect (model.py:130)")
-                vals[yi] = ([(ref, c, shr + 1) for ref, c, shr in parts], level - 1)
-                rules[yi] = ("up", resolve(m.f, yi))
-            elif kind == "Concat":
-                srcs = [resolve(f, yi) for f in m.f]
-                if len({vals[j][1] for j in srcs}) != 1:
-                    raise NotImplementedError(f"head row {k}: Concat of different resolutions")
-                vals[yi] = (sum((vals[j][0] for j in srcs), []), vals[srcs[0]][1])
-                rules[yi] = ("cat", srcs)
-            elif kind == "Detect":
-                if k != len(d) - 1 or len(m.f) != 1:
-                    raise NotImplementedError("Detect must be the last row with one input")
-                parts, level = vals[resolve(m.f[0], yi)]
-                if len(parts) != 1 or parts[0][0][0] != "unit" or parts[0][2] != 0 or level != 0:
-                    raise NotImplementedError("Detect reads one unit output on the stride-4 grid (model.py:130: stride = [4.])")
-                uses[parts[0][0]] = uses.get(parts[0][0], 0) + 1
-                self.head_out = (parts[0][0][1], parts[0][1])          # (unit row, channels)
-            else:
-                raise NotImplementedError(f"head row {k}: module {kind} is outside the hot path (SURVEY.md section 8)")
-        for ref in [("enc", j) for j in range(3)] + [("unit", u["k"]) for u in units]:
-            if uses.get(ref, 0) != 1:
-                raise NotImplementedError(f"head: {ref} is consumed {uses.get(ref, 0)} times; the hand-written backward routes every "
-                                          "feature to exactly one consumer")
-        self.head_units, self.head_rules, self.nd = units, rules, len(d) - 1
-        self.det_name = f"detect.{self.nd}."
-        self.sr_taps = None
-        if self.sr:
-            # model_up(y[l1], y[l2]) (model.py:286) cannot run with the yaml's l1 / l2 = 4 / 8 (256 channels into the 128-channel
-            # conv1); the taps are the first feature-list entries with the channel counts and grids DeepLab(ch, c1, c2) needs:
-            # c1 on the stride-4 grid (low-level) and c2 on the stride-8 grid - y[8] and y[5] in models/model.yaml
-            mu = self.model.model_up
-            def first(cn, level):
-                for yi in sorted(vals):
-                    if vals[yi][1] == level and sum(c for _, c, _ in vals[yi][0]) == cn:
-                        return yi
-                raise NotImplementedError(f"sr=True: no feature-list entry has {cn} channels on the stride-{4 << level} grid")
-            def fits(yi, cn, level):
-                return yi in vals and vals[yi][1] == level and sum(c for _, c, _ in vals[yi][0]) == cn
-            l1, l2 = getattr(self.model, "l1", None), getattr(self.model, "l2", None)
-            if fits(l1, mu.c1, 0) and fits(l2, mu.c2, 1):
-                self.sr_taps = (l1, l2)                      # the yaml's own taps (model.py:286: model_up(y[l1], y[l2])) are usable
-            else:
-                self.sr_taps = (first(mu.c1, 0), first(mu.c2, 1))
-                warnings.warn(f"sr=True: y[l1={l1}] / y[l2={l2}] of the yaml do not have {mu.c1} channels on the stride-4 grid / {mu.c2} on the "
-                              f"stride-8 grid that DeepLab(c1, c2) takes; tapping y[{self.sr_taps[0]}] / y[{self.sr_taps[1]}] instead "
-                              "(DESIGN.md section 4.3: graph parity unpinned)")
-            self.sr_parts = (vals[self.sr_taps[0]][0], vals[self.sr_taps[1]][0])
-
-    def _unit_out_name(self, u):
-        return f"h{u['k']}" + {"Conv": ".y", "C3": ".cv3.y", "SPP": ".cv2.y"}[u["kind"]]
 
     # ------------------------------------------------------------------ gradients: one flat f32 buffer
     def _build_grad_buffer(self):
@@ -394,15 +332,7 @@ class Engine:
         dev = self.dev
         w: Dict[str, torch.Tensor] = {}
         wT: Dict[str, torch.Tensor] = {}
-        descs_t, descs_f = [], []
-
-        def add(desc_list, src, dst, dims, perm, dst_ld):
-            d = L.PrepDesc()
-            d.src, d.dst = src.data_ptr(), dst.data_ptr()
-            d.d0, d.d1, d.d2 = dims
-            d.p0, d.p1, d.p2 = perm
-            d.dst_ld = dst_ld
-            desc_list.append(d)
+        tab_t, tab_f = ops.PrepTable(), ops.PrepTable()       # run-dtype destinations / f32 destinations
 
         # run-dtype mirror of the whole parameter buffer: every weight whose GEMM layout [N][K] IS its storage layout (all
         # nn.Linear and 1x1 Conv2d weights, pos_embed) is a VIEW of it - no per-step permute / cast launch for them; f32 runs
@@ -431,9 +361,9 @@ class Engine:
                 w[n] = mview(n, (N, K))
             else:
                 w[n] = torch.zeros(Np, taps * K, device=dev, dtype=dt)       # [N][tap*K + k]
-                add(descs_t, p, w[n], (N, K, taps), (0, 2, 1), taps * K)
+                tab_t.add(p, w[n], (N, K, taps), (0, 2, 1), taps * K)
             wT[n] = torch.zeros(K, taps * Np, device=dev, dtype=dt)          # [K][tap*N + n]
-            add(descs_t, p, wT[n], (N, K, taps), (1, 2, 0), taps * Np)
+            tab_t.add(p, wT[n], (N, K, taps), (1, 2, 0), taps * Np)
         # Linear MLPs on the bf16 path keep only the activation: the backward GEMM recomputes the pre-activation from
         # [fc1.weight | fc2.weight^T] ([4C][2C]) in its first K half (SODT_EPI_DGELU_RC)
         wcat: Dict[str, torch.Tensor] = {}
@@ -443,8 +373,8 @@ class Engine:
                     Cc = p.shape[1]
                     p2 = self.params[n.replace("fc1", "fc2")]
                     wc = torch.zeros(4 * Cc, 2 * Cc, device=dev, dtype=dt)
-                    add(descs_t, p, wc, (4 * Cc, Cc, 1), (0, 2, 1), 2 * Cc)
-                    add(descs_t, p2, wc[:, Cc:], (Cc, 4 * Cc, 1), (1, 2, 0), 2 * Cc)
+                    tab_t.add(p, wc, (4 * Cc, Cc, 1), (0, 2, 1), 2 * Cc)
+                    tab_t.add(p2, wc[:, Cc:], (Cc, 4 * Cc, 1), (1, 2, 0), 2 * Cc)
                     wcat[n] = wc
         # 2x2-conv MLPs with fc1 folded into the convolution: composed weights (re-made every forward by sodt_convmlp_compose)
         cmlp: Dict[str, Dict[str, torch.Tensor]] = {}
@@ -461,13 +391,13 @@ class Engine:
         for n, p in self.params.items():
             if "relative_position_bias_table" in n:
                 bias_t[n] = torch.zeros(p.shape[1], p.shape[0], device=dev, dtype=torch.float32)
-                add(descs_f, p, bias_t[n], (p.shape[0], p.shape[1], 1), (1, 0, 2), p.shape[0])
+                tab_f.add(p, bias_t[n], (p.shape[0], p.shape[1], 1), (1, 0, 2), p.shape[0])
         fe = {k: torch.zeros(4 * 48 * (16 if k == "w" else 1), device=dev, dtype=torch.float32) for k in ("w", "b", "g", "be")}
         for ci, c in enumerate("rgbi"):
-            add(descs_f, self.params[E + f"channel_embed_{c}.proj.weight"], fe["w"][ci * 768:], (48, 16, 1), (0, 1, 2), 16)
-            add(descs_f, self.params[E + f"channel_embed_{c}.proj.bias"], fe["b"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
-            add(descs_f, self.params[E + f"chan_block.norm{ci + 1}.weight"], fe["g"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
-            add(descs_f, self.params[E + f"chan_block.norm{ci + 1}.bias"], fe["be"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
+            tab_f.add(self.params[E + f"channel_embed_{c}.proj.weight"], fe["w"][ci * 768:], (48, 16, 1), (0, 1, 2), 16)
+            tab_f.add(self.params[E + f"channel_embed_{c}.proj.bias"], fe["b"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
+            tab_f.add(self.params[E + f"chan_block.norm{ci + 1}.weight"], fe["g"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
+            tab_f.add(self.params[E + f"chan_block.norm{ci + 1}.bias"], fe["be"][ci * 48:], (48, 1, 1), (0, 1, 2), 1)
 
         # fused W-MSA block kernel (csrc/wmsa_block.hip): one stage-ordered parameter pack per eligible block
         wmsa: Dict[str, torch.Tensor] = {}
@@ -479,21 +409,14 @@ class Engine:
                 if nb > 0:
                     wmsa[E + f"{sname}.{i}."] = torch.zeros(nb // (2 if dt == torch.bfloat16 else 4), device=dev, dtype=dt)
 
-        def table(descs):
-            arr = (L.PrepDesc * len(descs))(*descs)
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            mx = max(d.d0 * d.d1 * d.d2 for d in descs)
-            return host.to(dev), len(descs), mx
-        P = dict(w=w, wT=wT, wcat=wcat, cmlp=cmlp, bias_t=bias_t, fe=fe, tab_t=table(descs_t), tab_f=table(descs_f), dt=dt,
-                 ones={}, keep=(descs_t, descs_f), wmsa=wmsa)
+        P = dict(w=w, wT=wT, wcat=wcat, cmlp=cmlp, bias_t=bias_t, fe=fe, tab_t=tab_t.upload(dev), tab_f=tab_f.upload(dev), dt=dt,
+                 ones={}, wmsa=wmsa)
         self.prep[dt] = P
         return P
 
     def _run_prep(self, P):
-        tt, nt, mt = P["tab_t"]
-        ops.prep_weights(tt, nt, mt, L.BF16 if P["dt"] == torch.bfloat16 else L.F32)
-        tf, nf, mf = P["tab_f"]
-        ops.prep_weights(tf, nf, mf, L.F32)
+        P["tab_t"].run(L.BF16 if P["dt"] == torch.bfloat16 else L.F32)
+        P["tab_f"].run(L.F32)
         p = self.params
         for pre, wpk in P["wmsa"].items():
             ops.wmsa_pack(p[pre + "attn.qkv.weight"], p[pre + "attn.qkv.bias"], p[pre + "attn.proj.weight"], p[pre + "attn.proj.bias"],
@@ -551,12 +474,12 @@ class Engine:
 
         def nchw(name, h, c):
             return b[name].view(B, h, h, c).permute(0, 3, 1, 2)
-        items = [nchw("f0", t, 256), nchw("f1", t // 2, 256), nchw("f2", t // 4, 512)] + [None] * self.nd
-        for u in self.head_units:
-            items[3 + u["k"]] = nchw(self._unit_out_name(u), t >> u["level"], u["c2"])
-        y = _LazyFeatures(items, self.head_rules)
+        items = [nchw("f0", t, 256), nchw("f1", t // 2, 256), nchw("f2", t // 4, 512)] + [None] * self.head.nd
+        for u in self.head.units:
+            items[3 + u.k] = nchw(u.out_name, t >> u.level, u.c2)
+        y = _LazyFeatures(items, self.head.rules)
         if self.model.materialize_features:
-            for i in sorted(self.head_rules):
+            for i in sorted(self.head.rules):
                 y[i]
         return y
 
@@ -602,9 +525,9 @@ class Engine:
         # (4) Detect: live (fresh output tensor every call)
         T1 = B * t * t
         pred = torch.empty(B, self.na, t, t, self.no, device=self.dev, dtype=torch.float32)
-        hu = next(u for u in self.head_units if u["k"] == self.head_out[0])
-        ops.gemm_nt([SegSpec(plan.bufs[self._unit_out_name(hu)])], P["w"][self.det_name + "m.0.weight"], pred, T1, self.na * self.no,
-                    self.head_out[1], bias=self.params[self.det_name + "m.0.bias"], detect=(self.na, self.no, t * t))
+        hrow, hc = self.head.head_out
+        ops.gemm_nt([SegSpec(self._ref_buf(plan, Ref("unit", hrow)))], P["w"][self.det_name + "m.0.weight"], pred, T1, self.na * self.no,
+                    hc, bias=self.params[self.det_name + "m.0.bias"], detect=(self.na, self.no, t * t))
         return pred
 
     def _replay(self, plan: Plan, key: str, calls, probes):
@@ -663,32 +586,32 @@ class Engine:
         T3 = B * H * H
         f2 = plan.buf("f2", (T3, 512))
         ops.gemm_nt([SegSpec(x)], w[E + "neck3.weight"], f2, T3, 512, 768)
-        # ---- head (models/model.yaml:65-74 and the variants _check_head accepts), token-major
+        # ---- head (models/model.yaml:65-74 and the variants headgraph.parse_head accepts), token-major
         self._head_fwd(plan, P)
 
     def _head_fwd(self, plan: Plan, P):
         B, t = plan.B, plan.S // 4
-        b = plan.bufs
-        for u in self.head_units:
-            H = t >> u["level"]
+        for u in self.head.units:
+            H = t >> u.level
             M = B * H * H
-            tag, pname = f"h{u['k']}", f"detect.{u['k']}."
-            plain = all(shr == 0 for _, _, shr in u["parts"]) and ((u["kind"] == "Conv" and u["ksize"] == 1) or u["kind"] == "SPP")
+            tag, pname = f"h{u.k}", f"detect.{u.k}."
+            plain = all(p.shr == 0 for p in u.parts) and ((u.kind == "Conv" and u.ksize == 1) or u.kind == "SPP")
             segs = []
-            for ref, c, shr in u["parts"]:
-                src = b[("f0", "f1", "f2")[ref[1]]] if ref[0] == "enc" else b[self._unit_out_name(self._unit(ref[1]))]
+            for ref, c, shr in u.parts:
+                src = self._ref_buf(plan, ref)
                 segs.append(SegSpec(src) if plain else SegSpec(src, c, 0, 0, 0, 1, shr, H >> shr, H >> shr))
-            if u["kind"] == "Conv":
-                if u["ksize"] == 3:
+            if u.kind == "Conv":
+                if u.ksize == 3:
                     segs = [SegSpec(s_.t, s_.klen, 0, dy, dx, 1, s_.shr, s_.Hi, s_.Wi) for (dy, dx) in TAPS3 for s_ in segs]
-                self._conv_fwd(plan, P, tag, pname, segs, None if plain else (H, H), M, u["c1"] * u["ksize"] ** 2, u["c2"], u["ksize"])
-            elif u["kind"] == "C3":
-                self._c3_fwd(plan, P, tag, pname, segs, (H, H), M, u["c1"], u["c2"])
+                self._conv_fwd(plan, P, tag, pname, segs, None if plain else (H, H), M, u.c1 * u.ksize ** 2, u.c2, u.ksize)
+            elif u.kind == "C3":
+                self._c3_fwd(plan, P, tag, pname, segs, (H, H), M, u.c1, u.c2)
             else:
-                self._spp_fwd(plan, P, tag, pname, segs, (H, H), M, u["c1"], u["c2"], B)
+                self._spp_fwd(plan, P, tag, pname, segs, (H, H), M, u.c1, u.c2, B)
 
-    def _unit(self, k):
-        return next(u for u in self.head_units if u["k"] == k)
+    def _ref_buf(self, plan, ref):
+        """the plan buffer a headgraph.Ref names: an encoder output or a head unit's output"""
+        return plan.bufs[f"f{ref.index}" if ref.kind == "enc" else self.head.by_row[ref.index].out_name]
 
     # ------------------------------------------------------------------ Swin block
     def _block_geo(self, blk, H, W):
@@ -705,224 +628,249 @@ class Engine:
                              f"{blk.attn.window_size[0]}-window bias table; build Model with the matching img_size")
         return ws, shift
 
+    def _block_route(self, plan, P, tag, blk, x_in, B, H, W) -> BlockRoute:
+        """Decide, once, which launches run this block: the forward follows the record and the backward reads it back."""
+        pre = E + tag + "."
+        Cc, M = blk.dim, B * H * W
+        ws, shift = self._block_geo(blk, H, W)
+        # Resolution not a multiple of the window: the reference zero-pads AFTER norm1 and crops after the attention
+        # (backbone_vit.py:619-672, window_partition / window_unpartition), so a pad token enters the attention as the qkv BIAS.
+        # Unshifted blocks (stage 3 at S = 640, 768, ...: 40 x 40, 48 x 48 tokens against the 32-token window) run through the
+        # spatial K-segments: the QKV GEMM writes the padded grid (rows outside read zeros), the attention runs on it, the
+        # projection reads it back cropped.  Shifted blocks would also need the reference's mask of the UNPADDED grid: not built.
+        Hp, Wp = H + (-H) % ws, W + (-W) % ws
+        pad = (Hp, Wp) if (Hp, Wp) != (H, W) else None
+        if pad and shift > 0:
+            raise NotImplementedError(f"{tag}: {H}x{W} tokens are not a multiple of the {ws}-token window of a SHIFTED block (the "
+                                      "reference's zero padding, backbone_vit.py:619-643, is built for unshifted blocks only): choose "
+                                      "an input size S that is a multiple of 64")
+        wpk = P["wmsa"].get(pre) if (ws == 8 and H % 8 == 0 and W % 8 == 0) else None
+        if wpk is not None:
+            # q / k / v are saved by the f32 parity kernel only (sodt_window_attn_bwd_wm reads them back); the bf16 backward
+            # recomputes them from xn1 and the parameter pack (sodt_wmsa_block_bwd): 604 MB less written per launch
+            attn = ATTN_FUSED_SAVED if plan.dt == torch.float32 else ATTN_FUSED_RC
+        else:
+            attn = ATTN_PADDED if pad else ATTN_PLAIN
+        if blk.mlp.linear:
+            # Linear MLPs on the bf16 path keep only GELU(h): the backward recomputes h inside the dh GEMM
+            rc = ops.mlp_recompute_ok(M, Cc, plan.dt) and (pre + "mlp.fc1.weight") in P["wcat"]
+            if rc and self.use_fused_mlp and ops.mlp_fused_ok(M, Cc, plan.dt):
+                mlp = MLP_FUSED
+            else:
+                mlp = MLP_LIN_RC if rc else MLP_LIN_SAVED
+        else:
+            mlp = MLP_FOLD if pre in P["cmlp"] else MLP_CONV
+        return BlockRoute(x_in, (B, H, W, Cc, ws, shift), pad, attn, wpk, mlp, zscratch=wpk is None and ws * ws > 64,
+                          sq_ok=pad is None and plan.dt == torch.bfloat16 and Cc == 192)
+
     def _block_fwd(self, plan, P, tag, blk, x_in, B, H, W):
         ops.set_tag(tag)
+        r = plan.saved[tag] = self._block_route(plan, P, tag, blk, x_in, B, H, W)
+        xm, xn2 = self._attn_fwd(plan, P, tag, r)
+        return self._mlp_fwd(plan, P, tag, r, xm, xn2)
+
+    def _attn_fwd(self, plan, P, tag, r: BlockRoute):
+        """xm = x_in + proj(attention(LN1(x_in))), xn2 = LN2(xm); returns (xm, xn2)."""
         p, w = self.params, P["w"]
         pre = E + tag + "."
-        Cc = blk.dim
+        x_in, (B, H, W, Cc, ws, shift) = r.x_in, r.geo
         M = B * H * W
-        ws, shift = self._block_geo(blk, H, W)
+        bias_t = P["bias_t"][pre + "attn.relative_position_bias_table"]
         xn1 = plan.buf(tag + ".xn1", (M, Cc))
         st1 = plan.buf(tag + ".st1", (M, 2), torch.float32)
         xm = plan.buf(tag + ".xm", (M, Cc))
         xn2 = plan.buf(tag + ".xn2", (M, Cc))
         st2 = plan.buf(tag + ".st2", (M, 2), torch.float32)
-        ao = plan.buf(tag + ".ao", (M, Cc))
-        wpk = P["wmsa"].get(pre) if (ws == 8 and H % 8 == 0 and W % 8 == 0) else None
-        fused = wpk is not None
-        # Resolution not a multiple of the window: the reference zero-pads AFTER norm1 and crops after the attention
-        # (backbone_vit.py:619-672, window_partition / window_unpartition), so a pad token enters the attention as the qkv BIAS.
-        # Unshifted blocks (stage 3 at S = 640, 768, ...: 40 x 40, 48 x 48 tokens against the 32-token window) run here through the
-        # spatial K-segments: the QKV GEMM writes the padded grid (rows outside read zeros), the attention runs on it, the
-        # projection reads it back cropped.  Shifted blocks would also need the reference's mask of the UNPADDED grid: not built.
-        Hp, Wp = H + (-H) % ws, W + (-W) % ws
-        padded = (Hp, Wp) != (H, W)
-        if padded and shift > 0:
-            raise NotImplementedError(f"{tag}: {H}x{W} tokens are not a multiple of the {ws}-token window of a SHIFTED block (the "
-                                      "reference's zero padding, backbone_vit.py:619-643, is built for unshifted blocks only): choose "
-                                      "an input size S that is a multiple of 64")
-        if fused:
+        if r.attn in (ATTN_FUSED_RC, ATTN_FUSED_SAVED):
             # LN1 + QKV + window attention + proj + residual + LN2 in ONE launch (csrc/wmsa_hg.hip / wmsa_block.hip); training also
             # writes what the backward needs: xn1, the attention output, the LayerNorm statistics and the window-major
-            # log-sum-exp.  q / k / v are saved by the f32 parity kernel only (sodt_window_attn_bwd_wm reads them back); the bf16
-            # backward recomputes them from xn1 and the parameter pack (sodt_wmsa_block_bwd): 604 MB less written per launch
-            qkvw = plan.buf(tag + ".qkvw", (M // 64, HEADS, 3, 64, Cc // HEADS)) if (plan.training and plan.dt == torch.float32) else None
+            # log-sum-exp (and q / k / v where the backward reads them back)
+            ao = plan.buf(tag + ".ao", (M, Cc))
+            qkvw = plan.buf(tag + ".qkvw", (M // 64, HEADS, 3, 64, Cc // HEADS)) if (plan.training and r.attn == ATTN_FUSED_SAVED) else None
             lsew = plan.buf(tag + ".lsew", (M // 64, HEADS, 64), torch.float32)
             if plan.training:
-                ops.wmsa_block_fwd(x_in, wpk, xm, xn2, st1, st2, xn1, qkvw, lsew, ao, B, H, W, Cc, HEADS, ws, shift)
+                ops.wmsa_block_fwd(x_in, r.wpk, xm, xn2, st1, st2, xn1, qkvw, lsew, ao, B, H, W, Cc, HEADS, ws, shift)
             else:
-                ops.wmsa_block_fwd(x_in, wpk, xm, xn2, None, None, None, None, None, None, B, H, W, Cc, HEADS, ws, shift)
-        elif padded:
+                ops.wmsa_block_fwd(x_in, r.wpk, xm, xn2, None, None, None, None, None, None, B, H, W, Cc, HEADS, ws, shift)
+            return xm, xn2
+        ops.layernorm_fwd(x_in, p[pre + "norm1.weight"], p[pre + "norm1.bias"], xn1, st1, M, Cc)
+        if r.attn == ATTN_PADDED:
+            Hp, Wp = r.pad
             Mp = B * Hp * Wp
-            ops.layernorm_fwd(x_in, p[pre + "norm1.weight"], p[pre + "norm1.bias"], xn1, st1, M, Cc)
             qkv = plan.buf(tag + ".qkv", (Mp, 3 * Cc))
             ops.gemm_nt([SegSpec(xn1, Cc, 0, 0, 0, 1, 0, H, W)], w[pre + "attn.qkv.weight"], qkv, Mp, 3 * Cc, Cc, spatial=(Hp, Wp),
                         bias=p[pre + "attn.qkv.bias"])
             lse = plan.buf(tag + ".lse", (Mp, HEADS), torch.float32)
             aop = plan.buf(tag + ".aop", (Mp, Cc))
-            ops.window_attn_fwd(qkv, P["bias_t"][pre + "attn.relative_position_bias_table"], aop, lse, B, Hp, Wp, Cc, HEADS, ws, 0)
+            ops.window_attn_fwd(qkv, bias_t, aop, lse, B, Hp, Wp, Cc, HEADS, ws, 0)
             ops.gemm_nt([SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, spatial=(H, W),
                         bias=p[pre + "attn.proj.bias"], resid=x_in)
-            ops.layernorm_fwd(xm, p[pre + "norm2.weight"], p[pre + "norm2.bias"], xn2, st2, M, Cc)
         else:
-            ops.layernorm_fwd(x_in, p[pre + "norm1.weight"], p[pre + "norm1.bias"], xn1, st1, M, Cc)
+            ao = plan.buf(tag + ".ao", (M, Cc))
             qkv = plan.buf(tag + ".qkv", (M, 3 * Cc))
             ops.gemm_nt([SegSpec(xn1)], w[pre + "attn.qkv.weight"], qkv, M, 3 * Cc, Cc, bias=p[pre + "attn.qkv.bias"])
             lse = plan.buf(tag + ".lse", (M, HEADS), torch.float32)
-            ops.window_attn_fwd(qkv, P["bias_t"][pre + "attn.relative_position_bias_table"], ao, lse, B, H, W, Cc, HEADS, ws, shift)
+            ops.window_attn_fwd(qkv, bias_t, ao, lse, B, H, W, Cc, HEADS, ws, shift)
             ops.gemm_nt([SegSpec(ao)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, bias=p[pre + "attn.proj.bias"], resid=x_in)
-            ops.layernorm_fwd(xm, p[pre + "norm2.weight"], p[pre + "norm2.bias"], xn2, st2, M, Cc)
+        ops.layernorm_fwd(xm, p[pre + "norm2.weight"], p[pre + "norm2.bias"], xn2, st2, M, Cc)
+        return xm, xn2
+
+    def _mlp_fwd(self, plan, P, tag, r: BlockRoute, xm, xn2):
+        """xo = xm + MLP(xn2); returns xo."""
+        p, w = self.params, P["w"]
+        pre = E + tag + "."
+        B, H, W, Cc, _, _ = r.geo
+        M = B * H * W
         xo = plan.buf(tag + ".xo", (M, Cc))
-        if blk.mlp.linear and self.use_fused_mlp and ops.mlp_fused_ok(M, Cc, plan.dt) and ops.mlp_recompute_ok(M, Cc, plan.dt) and (pre + "mlp.fc1.weight") in P["wcat"]:
+        if r.mlp == MLP_FUSED:
             # fc1 + GELU + fc2 + residual in ONE launch (csrc/mlp.hip): the 4C-wide hidden activation leaves the CU only in training,
             # as GELU(h) for fc2's weight gradient (the backward recomputes h inside the dh GEMM, as below)
             ha = plan.buf(tag + ".ha", (M, 4 * Cc)) if plan.training else None
             ops.mlp_fwd(xn2, w[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], w[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"],
                         xm, xo, ha, M, Cc)
-        elif blk.mlp.linear:
+        elif r.mlp in (MLP_LIN_RC, MLP_LIN_SAVED):
             ha = plan.buf(tag + ".ha", (M, 4 * Cc))
-            if ops.mlp_recompute_ok(M, Cc, ha.dtype) and (pre + "mlp.fc1.weight") in P["wcat"]:
+            if r.mlp == MLP_LIN_RC:
                 # only GELU(h) is written; backward recomputes h inside the dh GEMM
                 ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], ha, M, 4 * Cc, Cc, bias=p[pre + "mlp.fc1.bias"], gelu_only=True)
             else:
                 hp = plan.buf(tag + ".hp", (M, 4 * Cc))
                 ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], hp, M, 4 * Cc, Cc, bias=p[pre + "mlp.fc1.bias"], gelu_out=ha)
             ops.gemm_nt([SegSpec(ha)], w[pre + "mlp.fc2.weight"], xo, M, Cc, 4 * Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
-        elif pre in P["cmlp"]:
-            # fc1 folded into the 2x2 convolution (csrc/convmlp.hip): composed weights, the convolution straight on xn2, a correction
-            # on the last column / row (where the padded fc1 output is zero including its bias)
-            cm = P["cmlp"][pre]
-            ops.convmlp_compose(p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"], p[pre + "mlp.conv1.bias"],
-                                cm["weff"], cm["weffT"], cm["beff"], cm["vtap"], Cc)
-            cp = plan.buf(tag + ".cp", (M, Cc))
-            ca = plan.buf(tag + ".ca", (M, Cc))
-            segs = [SegSpec(xn2, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_nt(segs, cm["weff"], cp, M, Cc, 4 * Cc, spatial=(H, W), bias=cm["beff"], gelu_out=ca)
-            ops.convmlp_border_fix(cp, ca, cm["vtap"], B, H, W, Cc)
-            ops.gemm_nt([SegSpec(ca)], w[pre + "mlp.fc2.weight"], xo, M, Cc, Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
         else:
-            u = plan.buf(tag + ".u", (M, Cc))
-            ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], u, M, Cc, Cc, bias=p[pre + "mlp.fc1.bias"])
+            if r.mlp == MLP_FOLD:
+                # fc1 folded into the 2x2 convolution (csrc/convmlp.hip): composed weights, the convolution straight on xn2, a
+                # correction on the last column / row (where the padded fc1 output is zero including its bias)
+                cm = P["cmlp"][pre]
+                ops.convmlp_compose(p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"], p[pre + "mlp.conv1.bias"],
+                                    cm["weff"], cm["weffT"], cm["beff"], cm["vtap"], Cc)
+                src, wc, bc = xn2, cm["weff"], cm["beff"]
+            else:
+                src = plan.buf(tag + ".u", (M, Cc))
+                ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], src, M, Cc, Cc, bias=p[pre + "mlp.fc1.bias"])
+                wc, bc = w[pre + "mlp.conv1.weight"], p[pre + "mlp.conv1.bias"]
             cp = plan.buf(tag + ".cp", (M, Cc))
             ca = plan.buf(tag + ".ca", (M, Cc))
-            segs = [SegSpec(u, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_nt(segs, w[pre + "mlp.conv1.weight"], cp, M, Cc, 4 * Cc, spatial=(H, W), bias=p[pre + "mlp.conv1.bias"],
-                        gelu_out=ca)
+            segs = [SegSpec(src, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
+            ops.gemm_nt(segs, wc, cp, M, Cc, 4 * Cc, spatial=(H, W), bias=bc, gelu_out=ca)
+            if r.mlp == MLP_FOLD:
+                ops.convmlp_border_fix(cp, ca, cm["vtap"], B, H, W, Cc)
             ops.gemm_nt([SegSpec(ca)], w[pre + "mlp.fc2.weight"], xo, M, Cc, Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
-        plan.saved[tag] = dict(x_in=x_in, geo=(B, H, W, Cc, ws, shift), fused=fused, wpk=wpk, pad=(Hp, Wp) if padded else None)
         return xo
+
+    def _linear_bwd(self, P, name, dY, X, dX, M, N, K, *, bias=True, sq=False, dgelu_aux=None, ldy=None, y_off=0, resid=None):
+        """Backward of one nn.Linear / 1x1 convolution `name` ([N][K] weight): dW (and dbias) += dY^T X by sodt_gemm_tn, then
+        dX = dY W [* gelu'(dgelu_aux)] [+ resid] by sodt_gemm_nt; dY may be N columns at y_off of a wider buffer.  sq: try the
+        square one-launch form first (csrc/linbwd.hip: both from one read of dY; ops.linear_bwd_sq returns False where the entry
+        point refuses the layer, and the two launches run instead)."""
+        gw, gb, wT = self.g[name + ".weight"], self.g[name + ".bias"] if bias else None, P["wT"][name + ".weight"]
+        if sq and ops.linear_bwd_sq(dY, X, wT, dX, gw, M, dbias=gb, dgelu_aux=dgelu_aux):
+            return
+        ops.gemm_tn(dY, [SegSpec(X)], gw, M, N, K, dbias=gb, ldy=ldy, y_off=y_off)
+        ops.gemm_nt([SegSpec(dY, N, y_off)], wT, dX, M, K, N, dgelu_aux=dgelu_aux, resid=resid)
 
     def _block_bwd(self, plan, P, tag, blk, dY, dX):
         """dY: gradient wrt the block output; writes the gradient wrt the block input into dX."""
         ops.set_tag(tag + ".bwd")
+        r = plan.saved[tag]
+        dxm, dxn = self._mlp_bwd(plan, P, tag, r, dY)
+        self._attn_bwd(plan, P, tag, r, dxm, dxn, dX)
+
+    def _mlp_bwd(self, plan, P, tag, r: BlockRoute, dY):
+        """MLP and LayerNorm-2 backward; returns (dxm: gradient wrt xm, dxn: scratch the attention backward goes on with)."""
         p, wT, g, b = self.params, P["wT"], self.g, plan.bufs
         pre = E + tag + "."
-        sv = plan.saved[tag]
-        B, H, W, Cc, ws, shift = sv["geo"]
+        B, H, W, Cc, _, _ = r.geo
         M = B * H * W
-        x_in = sv["x_in"]
-        xm, xn2, xn1, ao = b[tag + ".xm"], b[tag + ".xn2"], b[tag + ".xn1"], b[tag + ".ao"]
-        dxn = plan.buf(f"g.dxn.{Cc}", (M, Cc))
-        dxm = plan.buf(f"g.dxm.{Cc}", (M, Cc))
-        # (ops.linear_bwd_sq returns False where the entry point refuses the layer: the two launches run instead)
-        linbwd = self.use_fused_linbwd and not sv.get("pad") and plan.dt == torch.bfloat16 and Cc == 192
-        if blk.mlp.linear:
+        xm, xn2 = b[tag + ".xm"], b[tag + ".xn2"]
+        dxn = plan.scratch("dxn", (M, Cc))
+        dxm = plan.scratch("dxm", (M, Cc))
+        sq = self.use_fused_linbwd and r.sq_ok          # a backward-only switch: read live
+        if r.mlp in (MLP_FUSED, MLP_LIN_RC, MLP_LIN_SAVED):
             ha = b[tag + ".ha"]
-            dh = plan.buf(f"g.dh.{Cc}", (M, 4 * Cc))
-            ops.gemm_tn(dY, [SegSpec(ha)], g[pre + "mlp.fc2.weight"], M, Cc, 4 * Cc, dbias=g[pre + "mlp.fc2.bias"])
-            if (tag + ".hp") in b:
-                ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dh, M, 4 * Cc, Cc, dgelu_aux=b[tag + ".hp"])
+            dh = plan.scratch("dh", (M, 4 * Cc))
+            if r.mlp == MLP_LIN_SAVED:
+                self._linear_bwd(P, pre + "mlp.fc2", dY, ha, dh, M, Cc, 4 * Cc, dgelu_aux=b[tag + ".hp"])
             else:       # dh = (dY fc2.weight) * gelu'(xn2 fc1.weight^T + b1): pre-activation recomputed in the first K half
+                ops.gemm_tn(dY, [SegSpec(ha)], g[pre + "mlp.fc2.weight"], M, Cc, 4 * Cc, dbias=g[pre + "mlp.fc2.bias"])
                 ops.gemm_nt([SegSpec(xn2), SegSpec(dY)], P["wcat"][pre + "mlp.fc1.weight"], dh, M, 4 * Cc, 2 * Cc,
                             bias=p[pre + "mlp.fc1.bias"], dgelu_rc=True)
-            ops.gemm_tn(dh, [SegSpec(xn2)], g[pre + "mlp.fc1.weight"], M, 4 * Cc, Cc, dbias=g[pre + "mlp.fc1.bias"])
-            dln2 = (dh, 4 * Cc)
-        elif pre in P["cmlp"]:
-            cm = P["cmlp"][pre]
+            self._linear_bwd(P, pre + "mlp.fc1", dh, xn2, dxn, M, 4 * Cc, Cc)
+        else:
             cp, ca = b[tag + ".cp"], b[tag + ".ca"]
-            dc = plan.buf(f"g.dc.{Cc}", (M, Cc))
-            if not (linbwd and ops.linear_bwd_sq(dY, ca, wT[pre + "mlp.fc2.weight"], dc, g[pre + "mlp.fc2.weight"], M,
-                                                 dbias=g[pre + "mlp.fc2.bias"], dgelu_aux=cp)):
-                ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
-                ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
-            # d(Weff) = dc^T xn2(taps) (+ the column sums of dc), then the parameter gradients of fc1 / conv1 by the chain rule
-            scr = plan.buf(f"g.cmlp.{Cc}", (Cc * 4 * Cc + 4 * Cc,), torch.float32)
-            dweff, colsum, bs = scr[: Cc * 4 * Cc].view(Cc, 4 * Cc), scr[Cc * 4 * Cc: Cc * 4 * Cc + Cc], scr[Cc * 4 * Cc + Cc:].view(3, Cc)
-            ops.zero_(scr)
-            segs = [SegSpec(xn2, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_tn(dc, segs, dweff, M, Cc, 4 * Cc, spatial=(H, W), dbias=colsum)
-            ops.convmlp_border_sums(dc, bs, B, H, W, Cc)
-            ops.convmlp_decompose(dweff, colsum, bs, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"],
-                                  g[pre + "mlp.conv1.weight"], g[pre + "mlp.conv1.bias"], g[pre + "mlp.fc1.weight"], g[pre + "mlp.fc1.bias"], Cc)
-            dln2 = None           # d(xn2) comes from ONE tap GEMM with the composed weights (no du, no du W1)
-        else:
-            u, cp, ca = b[tag + ".u"], b[tag + ".cp"], b[tag + ".ca"]
-            dc = plan.buf(f"g.dc.{Cc}", (M, Cc))
-            du = plan.buf(f"g.du.{Cc}", (M, Cc))
-            if not (linbwd and ops.linear_bwd_sq(dY, ca, wT[pre + "mlp.fc2.weight"], dc, g[pre + "mlp.fc2.weight"], M,
-                                                 dbias=g[pre + "mlp.fc2.bias"], dgelu_aux=cp)):
-                ops.gemm_tn(dY, [SegSpec(ca)], g[pre + "mlp.fc2.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc2.bias"])
-                ops.gemm_nt([SegSpec(dY)], wT[pre + "mlp.fc2.weight"], dc, M, Cc, Cc, dgelu_aux=cp)
-            segs = [SegSpec(u, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_tn(dc, segs, g[pre + "mlp.conv1.weight"], M, Cc, 4 * Cc, spatial=(H, W), dbias=g[pre + "mlp.conv1.bias"],
-                        kperm=(Cc, 4))
-            segs = [SegSpec(dc, Cc, 0, -dy, -dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_nt(segs, wT[pre + "mlp.conv1.weight"], du, M, Cc, 4 * Cc, spatial=(H, W))
-            ops.gemm_tn(du, [SegSpec(xn2)], g[pre + "mlp.fc1.weight"], M, Cc, Cc, dbias=g[pre + "mlp.fc1.bias"])
-            dln2 = (du, Cc)
-        # d(xn2) = dln2 @ fc1.weight, then the LayerNorm-2 backward (+ the residual path's dY).  (Rounds 4-5 carried a GEMM with the
-        # LayerNorm backward as its epilogue for the 192-column case: slower than these two launches, removed in round 6 -
-        # profiles/r04_lnfold_ab.md, DESIGN.md section 5.)
-        if dln2 is None:
-            segs = [SegSpec(dc, Cc, 0, -dy, -dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-            ops.gemm_nt(segs, cm["weffT"], dxn, M, Cc, 4 * Cc, spatial=(H, W))
-            ops.layernorm_bwd(dxn, xm, b[tag + ".st2"], p[pre + "norm2.weight"], dY, dxm, g[pre + "norm2.weight"], g[pre + "norm2.bias"], M, Cc)
-        else:
-            ops.gemm_nt([SegSpec(dln2[0])], wT[pre + "mlp.fc1.weight"], dxn, M, Cc, dln2[1])
-            ops.layernorm_bwd(dxn, xm, b[tag + ".st2"], p[pre + "norm2.weight"], dY, dxm, g[pre + "norm2.weight"], g[pre + "norm2.bias"], M, Cc)
-        # attention
-        if sv.get("pad"):
-            self._padded_attn_bwd(plan, P, tag, pre, sv, dxm, dxn, dX)
-            return
-        dao = dxn
-        if not (linbwd and ops.linear_bwd_sq(dxm, ao, wT[pre + "attn.proj.weight"], dao, g[pre + "attn.proj.weight"], M,
-                                             dbias=g[pre + "attn.proj.bias"])):
-            ops.gemm_tn(dxm, [SegSpec(ao)], g[pre + "attn.proj.weight"], M, Cc, Cc, dbias=g[pre + "attn.proj.bias"])
-            ops.gemm_nt([SegSpec(dxm)], wT[pre + "attn.proj.weight"], dao, M, Cc, Cc)
-        dqkv = plan.buf(f"g.dqkv.{Cc}", (M, 3 * Cc))
-        L2 = 2 * ws - 1
-        dbt = plan.buf(f"g.dbt.{L2}", (HEADS, L2 * L2), torch.float32, zero=True)
-        if sv["fused"] and plan.dt == torch.bfloat16:
-            ops.wmsa_block_bwd(xn1, sv["wpk"], P["bias_t"][pre + "attn.relative_position_bias_table"], dao, b[tag + ".lsew"],
-                               dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
-        elif sv["fused"]:
-            ops.window_attn_bwd_wm(b[tag + ".qkvw"], P["bias_t"][pre + "attn.relative_position_bias_table"], dao, b[tag + ".lsew"],
-                                   dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
-        else:
-            scratch = plan.buf(f"g.attn_scratch.{Cc}", (M * (Cc + HEADS),), torch.float32, zero=True) if ws * ws > 64 else None
-            ops.window_attn_bwd(b[tag + ".qkv"], P["bias_t"][pre + "attn.relative_position_bias_table"], ao, dao, b[tag + ".lse"], dqkv,
-                                dbt, scratch, B, H, W, Cc, HEADS, ws, shift)
-        ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
-        ops.gemm_tn(dqkv, [SegSpec(xn1)], g[pre + "attn.qkv.weight"], M, 3 * Cc, Cc, dbias=g[pre + "attn.qkv.bias"])
-        ops.gemm_nt([SegSpec(dqkv)], wT[pre + "attn.qkv.weight"], dxn, M, Cc, 3 * Cc)
-        ops.layernorm_bwd(dxn, x_in, b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"], g[pre + "norm1.bias"], M, Cc)
+            dc = plan.scratch("dc", (M, Cc))
+            self._linear_bwd(P, pre + "mlp.fc2", dY, ca, dc, M, Cc, Cc, sq=sq, dgelu_aux=cp)
+            bsegs = [SegSpec(dc, Cc, 0, -dy, -dx, 1, 0, H, W) for (dy, dx) in TAPS2]
+            if r.mlp == MLP_FOLD:
+                # d(Weff) = dc^T xn2(taps) (+ the column sums of dc), then the parameter gradients of fc1 / conv1 by the chain rule;
+                # d(xn2) comes from ONE tap GEMM with the composed weights (no du, no du W1)
+                cm = P["cmlp"][pre]
+                scr = plan.scratch("cmlp", (Cc * 4 * Cc + 4 * Cc,), torch.float32)
+                dweff, colsum, bs = scr[: Cc * 4 * Cc].view(Cc, 4 * Cc), scr[Cc * 4 * Cc: Cc * 4 * Cc + Cc], scr[Cc * 4 * Cc + Cc:].view(3, Cc)
+                ops.zero_(scr)
+                segs = [SegSpec(xn2, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
+                ops.gemm_tn(dc, segs, dweff, M, Cc, 4 * Cc, spatial=(H, W), dbias=colsum)
+                ops.convmlp_border_sums(dc, bs, B, H, W, Cc)
+                ops.convmlp_decompose(dweff, colsum, bs, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"],
+                                      g[pre + "mlp.conv1.weight"], g[pre + "mlp.conv1.bias"], g[pre + "mlp.fc1.weight"], g[pre + "mlp.fc1.bias"], Cc)
+                ops.gemm_nt(bsegs, cm["weffT"], dxn, M, Cc, 4 * Cc, spatial=(H, W))
+            else:
+                du = plan.scratch("du", (M, Cc))
+                segs = [SegSpec(b[tag + ".u"], Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
+                ops.gemm_tn(dc, segs, g[pre + "mlp.conv1.weight"], M, Cc, 4 * Cc, spatial=(H, W), dbias=g[pre + "mlp.conv1.bias"],
+                            kperm=(Cc, 4))
+                ops.gemm_nt(bsegs, wT[pre + "mlp.conv1.weight"], du, M, Cc, 4 * Cc, spatial=(H, W))
+                self._linear_bwd(P, pre + "mlp.fc1", du, xn2, dxn, M, Cc, Cc)
+        # dxn = d(xn2); the LayerNorm-2 backward adds the residual path's dY.  (Rounds 4-5 carried a GEMM with the LayerNorm backward
+        # as its epilogue for the 192-column case: slower than these two launches, removed in round 6 - profiles/r04_lnfold_ab.md,
+        # DESIGN.md section 5.)
+        ops.layernorm_bwd(dxn, xm, b[tag + ".st2"], p[pre + "norm2.weight"], dY, dxm, g[pre + "norm2.weight"], g[pre + "norm2.bias"], M, Cc)
+        return dxm, dxn
 
-    def _padded_attn_bwd(self, plan, P, tag, pre, sv, dxm, dxn, dX):
-        """Attention half of the backward of an UNSHIFTED block whose resolution is not a multiple of its window (see _block_fwd): the
-        projection's input gradient lands on the padded grid (zeros outside: the crop's adjoint), the attention backward runs on it,
-        qkv.weight sees zero rows for the pad tokens while qkv.bias collects their gradient (their q / k / v ARE the bias), and the
-        input gradient is read back cropped."""
+    def _attn_bwd(self, plan, P, tag, r: BlockRoute, dxm, dxn, dX):
+        """Attention and LayerNorm-1 backward: dX = d(x_in) from dxm = d(xm); dxn is scratch (the projection's input gradient, then
+        d(xn1)).  The padded arm is the backward of an UNSHIFTED block whose resolution is not a multiple of its window (see
+        _block_route): the projection's input gradient lands on the padded grid (zeros outside: the crop's adjoint), the attention
+        backward runs on it, qkv.weight sees zero rows for the pad tokens while qkv.bias collects their gradient (their q / k / v
+        ARE the bias), and the input gradient is read back cropped."""
         p, wT, g, b = self.params, P["wT"], self.g, plan.bufs
-        B, H, W, Cc, ws, _ = sv["geo"]
-        Hp, Wp = sv["pad"]
-        M, Mp = B * H * W, B * Hp * Wp
-        aop, qkv, lse = b[tag + ".aop"], b[tag + ".qkv"], b[tag + ".lse"]
-        ops.gemm_tn(dxm, [SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], g[pre + "attn.proj.weight"], M, Cc, Cc, spatial=(H, W),
-                    dbias=g[pre + "attn.proj.bias"])
-        daop = plan.buf(f"g.daop.{Cc}", (Mp, Cc))
-        ops.gemm_nt([SegSpec(dxm, Cc, 0, 0, 0, 1, 0, H, W)], wT[pre + "attn.proj.weight"], daop, Mp, Cc, Cc, spatial=(Hp, Wp))
-        dqkv = plan.buf(f"g.dqkvp.{Cc}", (Mp, 3 * Cc))
+        pre = E + tag + "."
+        B, H, W, Cc, ws, shift = r.geo
+        M = B * H * W
+        xn1 = b[tag + ".xn1"]
+        bias_t = P["bias_t"][pre + "attn.relative_position_bias_table"]
         L2 = 2 * ws - 1
-        dbt = plan.buf(f"g.dbt.{L2}", (HEADS, L2 * L2), torch.float32, zero=True)
-        scratch = plan.buf(f"g.attn_scratchp.{Cc}", (Mp * (Cc + HEADS),), torch.float32, zero=True) if ws * ws > 64 else None
-        ops.window_attn_bwd(qkv, P["bias_t"][pre + "attn.relative_position_bias_table"], aop, daop, lse, dqkv, dbt, scratch,
-                            B, Hp, Wp, Cc, HEADS, ws, 0)
-        ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
-        ops.gemm_tn(dqkv, [SegSpec(b[tag + ".xn1"], Cc, 0, 0, 0, 1, 0, H, W)], g[pre + "attn.qkv.weight"], Mp, 3 * Cc, Cc,
-                    spatial=(Hp, Wp), dbias=g[pre + "attn.qkv.bias"])
-        ops.gemm_nt([SegSpec(dqkv, 3 * Cc, 0, 0, 0, 1, 0, Hp, Wp)], wT[pre + "attn.qkv.weight"], dxn, M, Cc, 3 * Cc, spatial=(H, W))
-        ops.layernorm_bwd(dxn, sv["x_in"], b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"],
-                          g[pre + "norm1.bias"], M, Cc)
+        if r.attn == ATTN_PADDED:
+            Hp, Wp = r.pad
+            Mp = B * Hp * Wp
+            aop = b[tag + ".aop"]
+            ops.gemm_tn(dxm, [SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], g[pre + "attn.proj.weight"], M, Cc, Cc, spatial=(H, W),
+                        dbias=g[pre + "attn.proj.bias"])
+            daop = plan.scratch("daop", (Mp, Cc))
+            ops.gemm_nt([SegSpec(dxm, Cc, 0, 0, 0, 1, 0, H, W)], wT[pre + "attn.proj.weight"], daop, Mp, Cc, Cc, spatial=(Hp, Wp))
+            dqkv = plan.scratch("dqkvp", (Mp, 3 * Cc))
+            dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
+            scratch = plan.scratch("attn_scratchp", (Mp * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
+            ops.window_attn_bwd(b[tag + ".qkv"], bias_t, aop, daop, b[tag + ".lse"], dqkv, dbt, scratch, B, Hp, Wp, Cc, HEADS, ws, 0)
+            ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
+            ops.gemm_tn(dqkv, [SegSpec(xn1, Cc, 0, 0, 0, 1, 0, H, W)], g[pre + "attn.qkv.weight"], Mp, 3 * Cc, Cc,
+                        spatial=(Hp, Wp), dbias=g[pre + "attn.qkv.bias"])
+            ops.gemm_nt([SegSpec(dqkv, 3 * Cc, 0, 0, 0, 1, 0, Hp, Wp)], wT[pre + "attn.qkv.weight"], dxn, M, Cc, 3 * Cc, spatial=(H, W))
+        else:
+            ao, dao = b[tag + ".ao"], dxn
+            self._linear_bwd(P, pre + "attn.proj", dxm, ao, dao, M, Cc, Cc, sq=self.use_fused_linbwd and r.sq_ok)
+            dqkv = plan.scratch("dqkv", (M, 3 * Cc))
+            dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
+            if r.attn == ATTN_FUSED_RC:
+                ops.wmsa_block_bwd(xn1, r.wpk, bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
+            elif r.attn == ATTN_FUSED_SAVED:
+                ops.window_attn_bwd_wm(b[tag + ".qkvw"], bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
+            else:
+                scratch = plan.scratch("attn_scratch", (M * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
+                ops.window_attn_bwd(b[tag + ".qkv"], bias_t, ao, dao, b[tag + ".lse"], dqkv, dbt, scratch, B, H, W, Cc, HEADS, ws, shift)
+            ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
+            self._linear_bwd(P, pre + "attn.qkv", dqkv, xn1, dxn, M, 3 * Cc, Cc)
+        ops.layernorm_bwd(dxn, r.x_in, b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"], g[pre + "norm1.bias"], M, Cc)
 
     # ------------------------------------------------------------------ PatchMerging
     def _merge_fwd(self, plan, P, tag, x, B, H, W, Cc):
@@ -963,6 +911,7 @@ class Engine:
         y = plan.buf(tag + ".y", (M, Cout)) if out is None else out
         ldy = y.shape[-1]
         wname = pname + "conv.weight"
+        direct = bool(plan.training and not self.fused and self._direct3(plan, segs, K, Cout, k))
         if self.fused:
             ones = P["ones"].setdefault(Cout, torch.ones(Cout, device=self.dev))
             ops.gemm_nt(segs, w[wname], y, M, Cout, K, spatial=spatial, affine=(ones, p[pname + "conv.bias"]), ldc=ldy)
@@ -970,7 +919,6 @@ class Engine:
             z = plan.buf(tag + ".z", (M, Cout))
             stats = plan.zbuf("f", tag + ".stats", (L.STATS_REPL, 2, Cout), torch.float64)   # zeroed with the pool (_forward_main)
             mr = plan.buf(tag + ".mr", (2, Cout), torch.float32)
-            direct = self._direct3(plan, segs, K, Cout, k)
             if direct:
                 # the 3x3 at 64 -> 64 channels of the stride-4 C3's Bottleneck: the direct kernel reads its input once (csrc/conv3.hip;
                 # the nine-segment GEMM ran at 0.11-0.15 of its HBM roofline), the batch statistics come from the stored output
@@ -987,8 +935,7 @@ class Engine:
             ops.bn_finalize(None, mr, bufs[pname + "bn.running_mean"], bufs[pname + "bn.running_var"], M, Cout, 1e-3, 0.03)
             ops.bn_affine(mr, p[pname + "bn.weight"], p[pname + "bn.bias"], sc[0], sc[1], Cout)
             ops.gemm_nt(segs, w[wname], y, M, Cout, K, spatial=spatial, affine=(sc[0], sc[1]), ldc=ldy)
-        plan.saved[tag] = dict(segs=segs, spatial=spatial, M=M, K=K, Cout=Cout, k=k, pname=pname,
-                               direct=bool(plan.training and not self.fused and self._direct3(plan, segs, K, Cout, k)))
+        plan.saved[tag] = ConvRoute(segs, spatial, M, K, Cout, k, pname, direct)
         return y
 
     def _direct3(self, plan, segs, K, Cout, k):
@@ -1004,7 +951,7 @@ class Engine:
         ops.set_tag(tag + ".bwd")
         p, g, b = self.params, self.g, plan.bufs
         sv = plan.saved[tag]
-        M, K, Cout, k, pname = sv["M"], sv["K"], sv["Cout"], sv["k"], sv["pname"]
+        M, K, Cout, k, pname = sv.M, sv.K, sv.Cout, sv.k, sv.pname
         red = plan.zbuf("b", tag + ".red", (2, Cout), torch.float64)                          # zeroed with the pool (_backward_main)
         dz = plan.buf(tag + ".dz", (M, Cout))
         ops.bn_silu_bwd_reduce(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, M, Cout,
@@ -1012,12 +959,12 @@ class Engine:
         ops.bn_silu_bwd_apply(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, dz,
                               g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off)
         cin = K // (k * k)
-        if sv.get("direct"):
-            H, W = sv["spatial"]
+        if sv.direct:
+            H, W = sv.spatial
             scr = plan.buf("g.c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
-            ops.conv3_c64_wgrad(dz, sv["segs"][4].t, g[pname + "conv.weight"], None, scr, M // (H * W), H, W)
+            ops.conv3_c64_wgrad(dz, sv.segs[4].t, g[pname + "conv.weight"], None, scr, M // (H * W), H, W)
         else:
-            ops.gemm_tn(dz, sv["segs"], g[pname + "conv.weight"], M, Cout, K, spatial=sv["spatial"],
+            ops.gemm_tn(dz, sv.segs, g[pname + "conv.weight"], M, Cout, K, spatial=sv.spatial,
                         kperm=(cin, k * k) if k > 1 else None)
         return dz
 
@@ -1047,7 +994,7 @@ class Engine:
         ops.gemm_nt([SegSpec(dzb)], wT[pname + "cv2.conv.weight"], din, M, c1, c_)
         dza3 = self._conv_bwd(plan, tag + ".m2", dcat, 2 * c_, 0)
         da = plan.buf(tag + ".da", (M, c_))
-        if plan.saved[tag + ".m2"].get("direct"):
+        if plan.saved[tag + ".m2"].direct:
             ops.conv3_c64_fwd(dza3, wT[pname + "m.0.cv2.conv.weight"], da, M // (H * W), H, W, flip=True)
         else:
             segs = [SegSpec(dza3, c_, 0, -dy, -dx, 1, 0, H, W) for (dy, dx) in TAPS3]
@@ -1093,16 +1040,13 @@ class Engine:
         return din
 
     # ================================================================== super-resolution branch (model.py:284-287)
-    def _ref_buf(self, plan, ref):
-        return plan.bufs[f"f{ref[1]}"] if ref[0] == "enc" else plan.bufs[self._unit_out_name(self._unit(ref[1]))]
-
     def _sr_forward(self, plan: Plan):
         """output_sr = model_up(low-level, deep) on the tapped features: live launches (sr.SRBranch; its weights are re-laid out
         from the masters every call).  The taps are K-segment views of the head's buffers - an Upsample / Concat entry is index
         arithmetic here too."""
         from .sr import SRBranch
         B, t = plan.B, plan.S // 4
-        br = getattr(plan, "sr", None)
+        br = plan.sr
         if br is None:
             names = [n for n in self.params if n.startswith("model_up.")]
             br = plan.sr = SRBranch({n: self.params[n] for n in names}, plan.dt, {n: self.g[n] for n in names},
@@ -1118,7 +1062,7 @@ class Engine:
         def segs(parts, level):
             h = t >> level
             return [SegSpec(self._ref_buf(plan, ref), c, 0, 0, 0, 1, shr, h >> shr, h >> shr) for ref, c, shr in parts]
-        return br.forward(segs(self.sr_parts[0], 0), segs(self.sr_parts[1], 1), B, t, t)
+        return br.forward(segs(self.head.sr_parts[0], 0), segs(self.head.sr_parts[1], 1), B, t, t)
 
     def _sr_backward(self, plan: Plan, dsr):
         """SR gradients: parameters into the flat buffer, inputs into plan.sr's dense buffers (zero when the SR output took no part
@@ -1135,12 +1079,13 @@ class Engine:
         """ref -> [(dense gradient buffer, ld, column offset, channels, shr)]: what the SR branch adds to d(feature)."""
         B, t = plan.B, plan.S // 4
         br = plan.sr
-        c1 = sum(c for _, c, _ in self.sr_parts[0])
-        c2 = sum(c for _, c, _ in self.sr_parts[1])
+        low, deep = self.head.sr_parts
+        c1 = sum(p.channels for p in low)
+        c2 = sum(p.channels for p in deep)
         d_low = br._buf("g.low", (B * t * t, c1))
         d_x = br._buf("g.x", (B * (t // 2) ** 2, c2))
         extra: Dict[tuple, list] = {}
-        for parts, buf, level in ((self.sr_parts[0], d_low, 0), (self.sr_parts[1], d_x, 1)):
+        for parts, buf, level in ((low, d_low, 0), (deep, d_x, 1)):
             coff = 0
             for ref, c, shr in parts:
                 extra.setdefault(ref, []).append((buf, buf.shape[1], coff, c, shr, t >> level))
@@ -1157,7 +1102,7 @@ class Engine:
                 ops.add_rows(dst, buf, B * H * H, c, ldd=ld, dcol=off, lds=lds, scol=coff)
             else:
                 Hs = H >> shr
-                tmp = plan.buf(f"sr.dup.{ref[0]}{ref[1]}.{i}", (B * Hs * Hs, c))
+                tmp = plan.buf(f"sr.dup.{ref.kind}{ref.index}.{i}", (B * Hs * Hs, c))
                 ops.gather_sum_rows(buf, lds, tmp, c, B, Hs, Hs, shr, c, d_off=coff)
                 ops.add_rows(dst, tmp, B * Hs * Hs, c, ldd=ld, dcol=off)
 
@@ -1211,7 +1156,7 @@ class Engine:
         gradient buffer.  The encoder has no cross-image coupling (LayerNorm, windows, per-image shifts), so a batch's encoder
         gradients are the sum of its images' - tests/test_fullsize_gpu.py checks the B = 8 training step that way.  Needs one
         ordinary backward on this plan first (it records the launches) and the activations of the latest forward."""
-        if plan.bwd_main is None or getattr(plan, "enc_bwd_start", None) is None:
+        if plan.bwd_main is None or plan.enc_bwd_start is None:
             raise RuntimeError("replay_encoder_backward: run one backward on this plan first")
         ops.replay(plan.bwd_main, start=plan.enc_bwd_start)
         self._frontend_bwd(plan, self._prep_for(plan.dt), x_rgb, x_ir)
@@ -1243,58 +1188,57 @@ class Engine:
         h2, h4 = t // 2, t // 4
         # ---- Detect
         dzd = b["g.dzd"]
-        hu = self._unit(self.head_out[0])
-        cd = self.head_out[1]
-        ops.gemm_tn(dzd, [SegSpec(b[self._unit_out_name(hu)])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np, lddw=cd,
+        hu = self.head.by_row[self.head.head_out[0]]
+        cd = self.head.head_out[1]
+        ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np, lddw=cd,
                     dbias=g[self.det_name + "m.0.bias"])
         dyd = plan.buf("g.dyd", (T1, cd))
         ops.gemm_nt([SegSpec(dzd)], wT[self.det_name + "m.0.weight"], dyd, T1, cd, self.det_np)
         # ---- head units in reverse: every unit returns d(its concatenated input) [M][c1]; the gradient of an Upsample /
         #      Concat input is a column slice of it (nearest x2^shr upsample: summed over the 2^shr x 2^shr children)
-        gout = {("unit", hu["k"]): (dyd, cd, 0)}                     # ref -> (buffer, ld, column offset)
+        gout = {hu.ref: (dyd, cd, 0)}                                # headgraph.Ref -> (buffer, ld, column offset)
         extra = self._sr_extra(plan) if self.sr else {}
-        for u in reversed(self.head_units):
-            H = t >> u["level"]
+        for u in reversed(self.head.units):
+            H = t >> u.level
             M = B * H * H
-            tag = f"h{u['k']}"
-            dy, ld, off = gout.pop(("unit", u["k"]))
-            self._add_extra(plan, extra, ("unit", u["k"]), (dy, ld, off))
-            if u["kind"] == "Conv":
+            tag = f"h{u.k}"
+            dy, ld, off = gout.pop(u.ref)
+            self._add_extra(plan, extra, u.ref, (dy, ld, off))
+            if u.kind == "Conv":
                 dz = self._conv_bwd(plan, tag, dy, ld, off)
-                din = plan.buf(tag + ".din", (M, u["c1"]))
-                w_ = wT[f"detect.{u['k']}.conv.weight"]
-                if u["ksize"] == 1:
-                    ops.gemm_nt([SegSpec(dz)], w_, din, M, u["c1"], u["c2"])
+                din = plan.buf(tag + ".din", (M, u.c1))
+                w_ = wT[f"detect.{u.k}.conv.weight"]
+                if u.ksize == 1:
+                    ops.gemm_nt([SegSpec(dz)], w_, din, M, u.c1, u.c2)
                 else:
-                    segs = [SegSpec(dz, u["c2"], 0, -dy_, -dx_, 1, 0, H, H) for (dy_, dx_) in TAPS3]
-                    ops.gemm_nt(segs, w_, din, M, u["c1"], 9 * u["c2"], spatial=(H, H))
-            elif u["kind"] == "C3":
+                    segs = [SegSpec(dz, u.c2, 0, -dy_, -dx_, 1, 0, H, H) for (dy_, dx_) in TAPS3]
+                    ops.gemm_nt(segs, w_, din, M, u.c1, 9 * u.c2, spatial=(H, H))
+            elif u.kind == "C3":
                 din = self._c3_bwd(plan, P, tag, dy, ld, off)
             else:
                 din = self._spp_bwd(plan, P, tag, dy, ld, off)
             coff = 0
-            for ref, c, shr in u["parts"]:
+            for ref, c, shr in u.parts:
                 if shr == 0:
-                    gout[ref] = (din, u["c1"], coff)
+                    gout[ref] = (din, u.c1, coff)
                 else:
                     Hs = H >> shr
                     dsrc = plan.buf(f"{tag}.dup{coff}", (B * Hs * Hs, c))
-                    ops.gather_sum_rows(din, u["c1"], dsrc, c, B, Hs, Hs, shr, c, d_off=coff)
+                    ops.gather_sum_rows(din, u.c1, dsrc, c, B, Hs, Hs, shr, c, d_off=coff)
                     gout[ref] = (dsrc, c, 0)
                 coff += c
         for j in range(3):
-            self._add_extra(plan, extra, ("enc", j), gout[("enc", j)])
-        (gf0, ld0, off0), (gf1, ld1, off1), (gf2, ld2, off2) = gout[("enc", 0)], gout[("enc", 1)], gout[("enc", 2)]
+            self._add_extra(plan, extra, Ref("enc", j), gout[Ref("enc", j)])
+        (gf0, ld0, off0), (gf1, ld1, off1), (gf2, ld2, off2) = (gout[Ref("enc", j)] for j in range(3))
         # where the head's backward ends and the encoder's begins, and the buffers the head left d(f0), d(f1), d(f2) in
         # (token-major rows, `ld` columns, the feature's columns at `off`): replay_encoder_backward re-runs the rest from there
         plan.enc_bwd_start = ops.recorded_count()
         plan.enc_gin = [(gf0, ld0, off0, 256), (gf1, ld1, off1, 256), (gf2, ld2, off2, 512)]
         # ---- neck3 + stage 3
         s3out = b["stage3.0.xo"]
-        ops.gemm_tn(gf2, [SegSpec(s3out)], g[E + "neck3.weight"], T3, 512, 768, ldy=ld2, y_off=off2)
         d3a = plan.buf("g.dA.768", (T3, 768))
         d3b = plan.buf("g.dB.768", (T3, 768))
-        ops.gemm_nt([SegSpec(gf2, 512, off2)], wT[E + "neck3.weight"], d3a, T3, 768, 512)
+        self._linear_bwd(P, E + "neck3", gf2, s3out, d3a, T3, 512, 768, bias=False, ldy=ld2, y_off=off2)
         self._block_bwd(plan, P, "stage3.0", enc.stage3[0], d3a, d3b)
         # head, neck 3 and stage 3 gradients are final: first data-parallel bucket (ddp.GradReducer.reduce_async)
         plan.bwd_marks.append((ops.recorded_count(), self.ddp_split3, self.flat_grad.numel()))
@@ -1303,8 +1247,7 @@ class Engine:
         dB = plan.buf("g.dB.384", (T2, 384))
         self._merge_bwd(plan, P, "pmerging2", d3b, dA)
         s2out = b["stage2.3.xo"]
-        ops.gemm_tn(gf1, [SegSpec(s2out)], g[E + "neck2.weight"], T2, 256, 384, ldy=ld1, y_off=off1)
-        ops.gemm_nt([SegSpec(gf1, 256, off1)], wT[E + "neck2.weight"], dA, T2, 384, 256, resid=dA)
+        self._linear_bwd(P, E + "neck2", gf1, s2out, dA, T2, 256, 384, bias=False, ldy=ld1, y_off=off1, resid=dA)
         cur, other = dA, dB
         for i in reversed(range(4)):
             self._block_bwd(plan, P, f"stage2.{i}", enc.stage2[i], cur, other)
@@ -1329,6 +1272,5 @@ class Engine:
         # ---- patch_embed 1x1 + pos_embed
         if plan.saved["use_pos"]:
             ops.batch_sum(cur, g[E + "pos_embed"], B, t * t * 192)
-        ops.gemm_tn(cur, [SegSpec(b["x0"])], g[E + "patch_embed.proj.weight"], T1, 192, 192, dbias=g[E + "patch_embed.proj.bias"])
         dx0 = plan.buf("g.dx0", (T1, 192))
-        ops.gemm_nt([SegSpec(cur)], wT[E + "patch_embed.proj.weight"], dx0, T1, 192, 192)
+        self._linear_bwd(P, E + "patch_embed.proj", cur, b["x0"], dx0, T1, 192, 192)

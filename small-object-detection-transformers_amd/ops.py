@@ -110,6 +110,9 @@ class SegSpec:
         self.coff, self.dy, self.dx, self.mul, self.shr, self.Hi, self.Wi = coff, dy, dx, mul, shr, Hi, Wi
 
 
+TAPS3 = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))     # (dy, dx) of a 3x3 convolution, kernel index (dy+1)*3 + dx+1
+
+
 def _fill_aspec(a: L.ASpec, segs: Sequence[SegSpec], spatial: Optional[Tuple[int, int]]):
     assert 1 <= len(segs) <= L.MAX_SEG
     es = segs[0].t.element_size()
@@ -630,6 +633,31 @@ def confusion_update(det, det_off, targets, geom, nc, conf, iou_thres, ws, matri
 
 def prep_weights(table_dev, n, max_elems, dtype_code):
     _launch("sodt_prep_weights", _p(table_dev), n, max_elems, dtype_code)
+
+
+class PrepTable:
+    """A descriptor table of sodt_prep_weights: add() one permuted copy per destination, upload() once, run() per step."""
+
+    def __init__(self):
+        self.descs: List[L.PrepDesc] = []
+        self.tab = None                 # (device table, descriptors, elements of the largest copy)
+
+    def add(self, src, dst, dims, perm, dst_ld, inner_ld=0):
+        d = L.PrepDesc()
+        d.src, d.dst = src.data_ptr(), dst.data_ptr()
+        d.d0, d.d1, d.d2 = dims
+        d.p0, d.p1, d.p2 = perm
+        d.dst_ld, d.inner_ld = dst_ld, inner_ld
+        self.descs.append(d)
+
+    def upload(self, dev):
+        arr = (L.PrepDesc * len(self.descs))(*self.descs)
+        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        self.tab = (host.to(dev), len(self.descs), max(d.d0 * d.d1 * d.d2 for d in self.descs))
+        return self
+
+    def run(self, dtype_code):
+        prep_weights(*self.tab, dtype_code)
 
 
 def transpose_f32(src, dst, rows, cols, accumulate=0):

@@ -29,9 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .ops import SegSpec
-
-TAPS3 = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))
+from .ops import TAPS3, SegSpec
 
 
 def sr_param_shapes(ch: int, c1: int, c2: int, depth: int = 16, width: int = 64) -> Dict[str, Tuple[int, ...]]:
@@ -112,7 +110,7 @@ class SRBranch:
         while f"{edsr}body.{self.depth}.body.0.weight" in params:
             self.depth += 1
         self.c: Dict[str, _Conv] = {}
-        descs = []
+        tab = ops.PrepTable()
         for k, v in params.items():
             if not k.endswith(".weight"):
                 continue
@@ -134,35 +132,23 @@ class SRBranch:
                 c.w = v.detach().view(c.cout, c.cin)
             else:
                 c.w = torch.zeros(c.np_, c.taps * c.cin, device=self.dev, dtype=dt)                 # [n][tap*Cin + c]
-                descs.append(self._desc(v, c.w, (c.cout, c.cin, c.taps), (0, 2, 1), c.taps * c.cin, 0))
+                tab.add(v, c.w, (c.cout, c.cin, c.taps), (0, 2, 1), c.taps * c.cin)
             c.wT = torch.zeros(c.cin, c.taps * c.np_, device=self.dev, dtype=dt)                      # [c][tap*Np + n]
-            descs.append(self._desc(v, c.wT, (c.cout, c.cin, c.taps), (1, 2, 0), c.taps * c.np_, c.np_ if c.np_ != c.cout else 0))
+            tab.add(v, c.wT, (c.cout, c.cin, c.taps), (1, 2, 0), c.taps * c.np_, c.np_ if c.np_ != c.cout else 0)
             # Upsampler stage (64 -> 256 + PixelShuffle 2, edsr.py:14-24) on the direct kernels: the input gradient of plane p = 2 i + j
             # wants wTp[p][k][tap * 64 + c] = W[4 c + p][k][tap] - the plain transpose of W viewed as [64 (c)][4 * 576 (p, k, tap)]
             c.wTp = None
             if dt == torch.bfloat16 and c.k == 3 and c.cin == 64 and c.cout == 256:
                 c.wTp = torch.zeros(4, 64, 576, device=self.dev, dtype=dt)
-                descs.append(self._desc(v, c.wTp, (64, 4 * 576, 1), (1, 2, 0), 64, 0))
+                tab.add(v, c.wTp, (64, 4 * 576, 1), (1, 2, 0), 64)
             self.c[c.name] = c
-        arr = (L.PrepDesc * len(descs))(*descs)
-        self._tab = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev), len(descs),
-                     max(d.d0 * d.d1 * d.d2 for d in descs))
+        self._tab = tab.upload(self.dev)
         self.bufs: Dict[str, torch.Tensor] = {}
         self.prepare()
 
-    @staticmethod
-    def _desc(src, dst, dims, perm, dst_ld, inner_ld):
-        d = L.PrepDesc()
-        d.src, d.dst = src.data_ptr(), dst.data_ptr()
-        d.d0, d.d1, d.d2 = dims
-        d.p0, d.p1, d.p2 = perm
-        d.dst_ld, d.inner_ld = dst_ld, inner_ld
-        return d
-
     def prepare(self):
         """(Re-)lay the float32 masters out for the GEMMs (one launch); call after every optimizer step."""
-        t, n, mx = self._tab
-        ops.prep_weights(t, n, mx, L.BF16 if self.dt == torch.bfloat16 else L.F32)
+        self._tab.run(L.BF16 if self.dt == torch.bfloat16 else L.F32)
         for c in self.c.values():
             if c.bias_pad is not None:
                 ops.cast(c.bias.detach(), c.bias_pad, c.cout)

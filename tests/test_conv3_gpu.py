@@ -304,7 +304,7 @@ def test_head_3x3_on_the_direct_kernels_matches_the_gemm_path():
         eng.use_direct_conv3 = direct
         pred, _ = m(x, ir, "RGB+IR")
         (pred[0].float() * torch.linspace(-1, 1, pred[0].numel(), device=dev).view_as(pred[0])).sum().backward()
-        used = [t for t, sv in next(iter(eng.plans.values())).saved.items() if isinstance(sv, dict) and sv.get("direct")]
+        used = [t for t, sv in next(iter(eng.plans.values())).saved.items() if getattr(sv, "direct", False)]
         assert bool(used) == direct, used
         grads = {n: p.grad.detach().float().clone() for n, p in m.named_parameters() if p.grad is not None}
         outs.append((pred[0].detach().float().clone(), grads))

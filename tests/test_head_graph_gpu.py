@@ -1,4 +1,4 @@
-"""Head graphs other than models/model.yaml:65-74 through ``Model(cfg)`` (engine._check_head / _head_fwd / the reverse walk in
+"""Head graphs other than models/model.yaml:65-74 through ``Model(cfg)`` (headgraph.parse_head / _head_fwd / the reverse walk in
 _backward_main): an SPP row (common.py:129-140, the row SRyolo_MF.yaml:46 uses) after detect.0, and a 3x3 Conv row.
 
 * tests/golden/spp_head_512.pt comes from the REAL reference: its own parse_model builds this head and forward_once runs it

@@ -241,14 +241,14 @@ def test_engine_block_backward_switch(dev):
     plan = next(p for p in eng.plans.values() if p.dt == BF and p.training)
     P = eng._prep_for(BF)
     tag, blk = "stage1.1", model.image_encoder.stage1[1]
-    Bq, H, W, Cc, ws, shift = plan.saved[tag]["geo"]
+    Bq, H, W, Cc, ws, shift = plan.saved[tag].geo
     assert (Bq, H, W, Cc, ws, shift) == (1, 64, 64, 192, 8, 2) and not blk.mlp.linear
     M = H * W
     gen = torch.Generator(device="cpu").manual_seed(9)
     dY = torch.randn(M, Cc, generator=gen).to(BF).to(dev)
     pre = "image_encoder." + tag + "."
     own = [pre + "attn.proj.weight", pre + "attn.proj.bias", pre + "mlp.fc2.weight", pre + "mlp.fc2.bias"]
-    acts = [f"g.dxm.{Cc}", f"g.dc.{Cc}", f"g.dqkv.{Cc}"]
+    acts = [f"g.dxm.{M}x{Cc}", f"g.dc.{M}x{Cc}", f"g.dqkv.{M}x{3 * Cc}"]     # Plan.scratch: kind and shape
     res = {}
     for on in (True, False):
         eng.use_fused_linbwd = on
@@ -266,7 +266,7 @@ def test_engine_block_backward_switch(dev):
     splits = max(1, min(M // 512, 256))
     k = (M / 32 + splits + 1) * 2.0 ** -24
     b = plan.bufs
-    pairs = {pre + "attn.proj": (res[True]["a"][f"g.dxm.{Cc}"].double(), b[tag + ".ao"].double()),
+    pairs = {pre + "attn.proj": (res[True]["a"][f"g.dxm.{M}x{Cc}"].double(), b[tag + ".ao"].double()),
              pre + "mlp.fc2": (dY.double(), b[tag + ".ca"].double())}
     for on in (True, False):
         for n in own:
