@@ -40,6 +40,7 @@ STAGE_DIMS = (192, 384, 768)        # backbone_vit.py:118,135,152
 STAGE_DEPTHS = (6, 4, 1)            # backbone_vit.py:116,133,150
 STAGE_WINDOWS = (8, 8, 32)          # backbone_vit.py:121,138,155
 SHIFTS = (0, 2, 0, 2, 0, 2, 0, 2)   # backbone_vit.py:114
+LOG2E = 1.4426950408889634           # the fused W-MSA parameter pack keeps the bias table x log2 e (csrc/wmsa_block.hip)
 LN_EPS = 1e-5                       # nn.LayerNorm default (Appendix B of SURVEY.md)
 BN_EPS = 1e-3                       # utils/torch_utils.py:150
 BN_MOMENTUM = 0.03                  # utils/torch_utils.py:151
@@ -185,65 +186,79 @@ def frontend(sd: SD, x4: Tensor, pfx: str = "image_encoder.", ca_window: int = 1
 # ----------------------------------------------------------------------------
 # Swin block
 # ----------------------------------------------------------------------------
-def window_attention(sd: SD, pfx: str, xw: Tensor, ws: int, mask: Optional[Tensor]) -> Tensor:
-    """WindowAttention.forward (backbone_vit.py:961-992)."""
+def window_attention(sd: SD, pfx: str, xw: Tensor, ws: int, mask: Optional[Tensor], store=None) -> Tensor:
+    """WindowAttention.forward (backbone_vit.py:961-992).  store: see swin_block."""
+    st = store if store is not None else (lambda t, name: t)
     B_, N, C = xw.shape
     hd = C // NUM_HEADS
-    qkv = (xw @ sd[pfx + "qkv.weight"].t() + sd[pfx + "qkv.bias"])
+    qkv = st(xw @ sd[pfx + "qkv.weight"].t() + sd[pfx + "qkv.bias"], "qkv")
     qkv = qkv.reshape(B_, N, 3, NUM_HEADS, hd).permute(2, 0, 3, 1, 4)
     q, k, v = qkv[0], qkv[1], qkv[2]
     q = q * (hd ** -0.5)
     attn = q @ k.transpose(-2, -1)
-    idx = relative_position_index(ws).view(-1)
-    bias = sd[pfx + "relative_position_bias_table"][idx].view(N, N, -1).permute(2, 0, 1).contiguous()
+    idx = relative_position_index(ws).view(-1).to(xw.device)
+    table = sd[pfx + "relative_position_bias_table"]
+    if store is not None:       # the one parameter the fused W-MSA pack stores narrowed beside the GEMM weights: table x log2 e
+        table = store(table * LOG2E, "table") / LOG2E
+    bias = table[idx].view(N, N, -1).permute(2, 0, 1).contiguous()
     attn = attn + bias.unsqueeze(0)
     if mask is not None:
         nW = mask.shape[0]
         attn = attn.view(B_ // nW, nW, NUM_HEADS, N, N) + mask.unsqueeze(1).unsqueeze(0)
         attn = attn.view(-1, NUM_HEADS, N, N)
-    attn = torch.softmax(attn, dim=-1)
-    x = (attn @ v).transpose(1, 2).reshape(B_, N, C)
+    attn = st(torch.softmax(attn, dim=-1), "p")
+    x = st((attn @ v).transpose(1, 2).reshape(B_, N, C), "ao")
     return x @ sd[pfx + "proj.weight"].t() + sd[pfx + "proj.bias"]
 
 
-def mlp(sd: SD, pfx: str, x: Tensor, H: int, W: int, linear: bool) -> Tensor:
-    """Mlp.forward (backbone_vit.py:884-908)."""
+def mlp(sd: SD, pfx: str, x: Tensor, H: int, W: int, linear: bool, store=None) -> Tensor:
+    """Mlp.forward (backbone_vit.py:884-908).  store: see swin_block."""
+    st = store if store is not None else (lambda t, name: t)
     if linear:
-        h = F.gelu(x @ sd[pfx + "fc1.weight"].t() + sd[pfx + "fc1.bias"])
+        h = st(F.gelu(st(x @ sd[pfx + "fc1.weight"].t() + sd[pfx + "fc1.bias"], "hp")), "ha")
         return h @ sd[pfx + "fc2.weight"].t() + sd[pfx + "fc2.bias"]
-    u = x @ sd[pfx + "fc1.weight"].t() + sd[pfx + "fc1.bias"]
+    u = st(x @ sd[pfx + "fc1.weight"].t() + sd[pfx + "fc1.bias"], "u")
     bs = u.shape[0]
     u = u.permute(0, 2, 1).contiguous().view(bs, -1, H, W)
     u = F.pad(u, (0, 1, 0, 1))                                     # :896 right/bottom zero pad
     u = F.conv2d(u, sd[pfx + "conv1.weight"], sd[pfx + "conv1.bias"])   # 2x2, :897
-    u = u.permute(0, 2, 3, 1).contiguous().view(bs, H * W, -1)
-    u = F.gelu(u)
+    u = st(u.permute(0, 2, 3, 1).contiguous().view(bs, H * W, -1), "cp")
+    u = st(F.gelu(u), "ca")
     return u @ sd[pfx + "fc2.weight"].t() + sd[pfx + "fc2.bias"]
 
 
-def swin_block(sd: SD, pfx: str, x: Tensor, H: int, W: int, window: int, shift: int, linear_mlp: bool) -> Tensor:
+def swin_block(sd: SD, pfx: str, x: Tensor, H: int, W: int, window: int, shift: int, linear_mlp: bool, store=None) -> Tensor:
     """SwinTransformerBlock.forward (backbone_vit.py:1084-1130) incl. the window
-    clamp of the ctor (:1042-1045)."""
+    clamp of the ctor (:1042-1045).
+
+    store(t, name) (default: the identity) is applied to every value a reduced-precision run of the block writes to memory or
+    feeds to a matrix unit narrowed: the block input "x" (its gradient on the way back), norm1's output "xn1", "qkv", the softmax
+    probabilities "p", the attention output "ao", the first residual sum "xm", norm2's output "xn2", the MLP's pre-activations and
+    activations "hp" / "ha" or "u" / "cp" / "ca", the block output "xo" (and "table", see window_attention).  The tests pass a
+    straight-through rounding function (tests/block_cases.py) to state a block's own rounding noise in float64, and read
+    intermediate values through the same hook."""
+    st = store if store is not None else (lambda t, name: t)
     B, L, C = x.shape
     assert L == H * W
     ws = window
     if min(H, W) <= ws:
         shift = 0
         ws = min(H, W)
+    x = st(x, "x")
     shortcut = x
-    xn = layer_norm(x, sd[pfx + "norm1.weight"], sd[pfx + "norm1.bias"]).view(B, H, W, C)
+    xn = st(layer_norm(x, sd[pfx + "norm1.weight"], sd[pfx + "norm1.bias"]), "xn1").view(B, H, W, C)
     mask = None
     if shift > 0:
         xn = torch.roll(xn, shifts=(-shift, -shift), dims=(1, 2))
-        mask = shift_mask(H, W, ws, shift, x.dtype)
+        mask = shift_mask(H, W, ws, shift, x.dtype).to(x.device)
     xw = window_partition(xn, ws).view(-1, ws * ws, C)
-    aw = window_attention(sd, pfx + "attn.", xw, ws, mask)
+    aw = window_attention(sd, pfx + "attn.", xw, ws, mask, store)
     xs = window_unpartition(aw.view(-1, ws, ws, C), ws, H, W)
     if shift > 0:
         xs = torch.roll(xs, shifts=(shift, shift), dims=(1, 2))
-    x = shortcut + xs.view(B, H * W, C)
-    xn2 = layer_norm(x, sd[pfx + "norm2.weight"], sd[pfx + "norm2.bias"])
-    return x + mlp(sd, pfx + "mlp.", xn2, H, W, linear_mlp)
+    x = st(shortcut + xs.view(B, H * W, C), "xm")
+    xn2 = st(layer_norm(x, sd[pfx + "norm2.weight"], sd[pfx + "norm2.bias"]), "xn2")
+    return st(x + mlp(sd, pfx + "mlp.", xn2, H, W, linear_mlp, store), "xo")
 
 
 def patch_merging(sd: SD, pfx: str, x: Tensor, H: int, W: int) -> Tensor:
