@@ -5,9 +5,11 @@
  * on its hot path is a torch.nn call.  Each entry point below therefore cites the
  * reference lines whose ATen op sequence it replaces (paths relative to the
  * reference root).  Conventions: raw device pointers + explicit sizes, caller-owned
- * memory (workspaces included), a hipStream_t argument, int return (0 = ok,
- * SODT_EINVAL = shape/alignment the kernel does not support -- nothing launched),
- * no allocation / synchronisation / exceptions inside; safe to capture in a hipGraph.
+ * memory (workspaces included), a hipStream_t argument, int return (SODT_OK;
+ * SODT_EINVAL = the arguments were checked and refused, a shape or alignment the kernel does not support -- nothing launched
+ * or written; SODT_ELAUNCH = the runtime failed a launch, an LDS opt-in, a memset or a sort -- earlier launches of the same
+ * call may already be queued, none after it is), no allocation / synchronisation / exceptions inside; safe to capture in a
+ * hipGraph.
  *
  * dtype: 0 = float32 (parity path, exact-f32 MFMA), 1 = bfloat16 (throughput path,
  * f32 accumulate).  Activations are token-major ("NHWC"): row = (b*H + y)*W + x,
@@ -24,6 +26,10 @@ extern "C" {
 #endif
 
 typedef struct ihipStream_t* sodt_stream_t;   /* == hipStream_t */
+
+#define SODT_OK 0
+#define SODT_EINVAL 1
+#define SODT_ELAUNCH 2
 
 #define SODT_F32 0
 #define SODT_BF16 1
@@ -95,8 +101,12 @@ typedef struct {
  * input-gradient GEMM of the path (backbone_vit.py:968,990,886-904,857,213,268-270;
  * common.py:43,49; model.py:53). */
 int sodt_gemm_nt(const sodt_gemm_args* g, int dtype, sodt_stream_t st);
-/* test hook: 1 forces the K-loop tile kernel even where the A-stationary kernel applies, 0 = automatic */
-int sodt_gemm_set_variant(int force_tiled);
+/* test hook: which kernels sodt_gemm_nt / sodt_gemm_tn may choose (nt_route / tn_route in csrc/routes.h) */
+#define SODT_VARIANT_AUTO 0      /* automatic */
+#define SODT_VARIANT_TILED 1     /* NT: the K-loop 128 x 128 kernel; TN: the 128 x 128 kernel */
+#define SODT_VARIANT_ASTAT 2     /* NT: A-stationary instead of B-stationary, no pipelined kernel; TN: without the pipelined kernel */
+#define SODT_VARIANT_NO_TN3 3    /* NT as automatic; TN without the pipelined kernel */
+int sodt_gemm_set_variant(int variant);
 
 typedef struct {
   const void* dY; int ldy;      /* [M][N] run dtype; ldy >= N rounded up to 16 bytes (pad columns must be zero) */
@@ -439,9 +449,9 @@ int sodt_nms_select(const float* z, int nc, const unsigned long long* keys, long
  *   (B, cap) int32): for each input row the output row of its cluster within its image, -1 for a dropped row.
  *   scan_lanes: lanes of the workgroup that walks one (image, label) segment, 64 or 256; 0 = the default.
  *   ws: 256-byte aligned scratch of at least sodt_wbf_fuse_workspace_bytes(B, cap) (one cluster per row at worst).
- *   B <= 65535, B * cap <= 2^30.  No entry allocates or synchronises.  Every argument is checked before the first launch;
- *   SODT_EINVAL is also what a failing runtime call (a memset, a rocPRIM sort) returns part-way, and only then may
- *   earlier launches of the same call already be queued. */
+ *   B <= 65535, B * cap <= 2^30.  No entry allocates or synchronises.  Every argument is checked before the first launch
+ *   (SODT_EINVAL); a failing runtime call (a memset, a rocPRIM sort, a launch) returns SODT_ELAUNCH part-way, and only then
+ *   may earlier launches of the same call already be queued. */
 int sodt_wbf_candidates(const float* z, int B, int N, int nc, float conf_thres, float image_size, float* boxes,
                         float* scores, int* labels, int* src, int* counts, sodt_stream_t st);
 int sodt_wbf_fuse_workspace_bytes(int B, long cap, size_t* bytes);

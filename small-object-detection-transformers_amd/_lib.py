@@ -23,6 +23,7 @@ def overrides():
     return {k: os.environ[k] for k in DIAGNOSTIC_ENV if os.environ.get(k)}
 
 MAX_SEG = 9
+EINVAL, ELAUNCH = 1, 2                                # SODT_EINVAL: refused, nothing launched; SODT_ELAUNCH: the runtime failed
 F32, BF16 = 0, 1
 U8 = 2                                                # SODT_U8: target dtype of sodt_sr_l1_fwd / _bwd
 SR_MODES = {"IR": 0, "RGB": 1, "RGB+IR": 2}           # SODT_SR_IR / SODT_SR_RGB / SODT_SR_RGB_IR

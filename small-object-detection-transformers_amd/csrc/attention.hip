@@ -19,16 +19,12 @@
 // small LDS table per head ((2R-1) x (2ws-1) <= 225 entries, R = 64/ws rows per tile)
 // and flushed with a few global atomics.
 #include "common.h"
+#include "launch.h"
+#include "routes.h"
 #include "wmsa_pack.h"
-#include "../../include/sodt_hip.h"
 #include <type_traits>
 
 namespace {
-
-struct AttnGeo {
-  int B, H, W, C, heads, ws, shift;
-  int nwy, nwx, N, nqt;   // windows per column/row, tokens per window, 64-token tiles per window
-};
 
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
@@ -2294,148 +2290,93 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_fwd_mt2_kern
   }
 }
 
-bool make_geo(AttnGeo& g, int B, int H, int W, int C, int heads, int ws, int shift) {
-  if (B <= 0 || H <= 0 || W <= 0 || ws <= 0 || (H % ws) || (W % ws) || heads <= 0 || (C % heads)) return false;
-  if ((ws * ws) % 64) return false;
-  if (ws < 8 || (64 % ws && ws < 64) ) return false;           // a 64-token tile must cover whole window rows
-  if (ws > 64) return false;
-  if (shift < 0 || shift >= ws) return false;
-  g.B = B; g.H = H; g.W = W; g.C = C; g.heads = heads; g.ws = ws; g.shift = shift;
-  g.nwy = H / ws; g.nwx = W / ws; g.N = ws * ws; g.nqt = g.N / 64;
-  return true;
+template <typename T> constexpr int DTYPE = std::is_same<T, bf16>::value ? SODT_BF16 : SODT_F32;
+
+// The launchers run what attn_*_route (routes.h) chose.  Their `if constexpr` guards only keep a kernel that does not compile
+// for a (T, HD) from being instantiated; the route never names such a kernel.
+template <typename T, int HD>
+int launch_fwd(AttnFwdKind kind, const void* qkv, const float* bias_t, void* out, float* lse, const AttnGeo& g, hipStream_t st) {
+  constexpr int NW = attn_nw(DTYPE<T>, HD, false);
+  const int nwin = g.B * g.nwy * g.nwx;
+  const dim3 mt_grid((unsigned)((long)nwin * (g.nqt / 4) * g.heads));
+  switch (kind) {
+    case AF_FAST:
+      if constexpr (3 * Lay<T, HD>::DCH <= 12)
+        return sodt_launch<attn_fwd_fast_kernel<T, HD, NW>>(dim3(attn_fwd_fast_grid(nwin), g.heads / NW), dim3(NW * 64), 0, st,
+                                                            (const T*)qkv, bias_t, (T*)out, lse, g, nwin);
+      break;
+    case AF_MT2:
+      if constexpr (attn_mt2_built(DTYPE<T>, HD))
+        return sodt_launch<attn_fwd_mt2_kernel<T, HD>>(mt_grid, dim3(256), 0, st, (const T*)qkv, bias_t, (T*)out, lse, g);
+      break;
+    case AF_MT:
+      if constexpr (attn_mt1_built(DTYPE<T>, HD))
+        return sodt_launch<attn_fwd_mt_kernel<T, HD>>(mt_grid, dim3(256), 0, st, (const T*)qkv, bias_t, (T*)out, lse, g);
+      break;
+    case AF_GENERIC:
+      return sodt_launch<attn_fwd_kernel<T, HD, NW>>(dim3((unsigned)((long)nwin * g.nqt * (g.heads / NW))), dim3(NW * 64), 0, st,
+                                                     (const T*)qkv, bias_t, (T*)out, lse, g);
+  }
+  return SODT_EINVAL;
 }
 
-template <typename T, int HD, int NW>
-int launch_fwd(const void* qkv, const float* bias_t, void* out, float* lse, const AttnGeo& g, hipStream_t st) {
-  if (g.heads % NW) return SODT_EINVAL;
-  if constexpr (3 * Lay<T, HD>::DCH <= 12) {
-    if (g.nqt == 1) {
-      const int nwin = g.B * g.nwy * g.nwx;
-      const int gx = nwin < 512 ? nwin : 512;
-      hipLaunchKernelGGL((attn_fwd_fast_kernel<T, HD, NW>), dim3(gx, g.heads / NW), dim3(NW * 64), 0, st,
-                         (const T*)qkv, bias_t, (T*)out, lse, g, nwin);
-      return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
-    }
-  }
-  if constexpr (HD % TT<T>::MMA_K == 0 && Lay<T, HD>::DCH >= 4 && Lay<T, HD>::DCH <= 16) {
-    if (g.nqt > 1 && (g.nqt % 4) == 0 && g.shift == 0 && g.ws <= 32) {
-      const long nb = (long)g.B * g.nwy * g.nwx * (g.nqt / 4) * g.heads;
-      hipLaunchKernelGGL((attn_fwd_mt2_kernel<T, HD>), dim3((unsigned)nb), dim3(256), 0, st,
-                         (const T*)qkv, bias_t, (T*)out, lse, g);
-      return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
-    }
-  }
-  if constexpr (Lay<T, HD>::DCH >= 4 && Lay<T, HD>::DCH <= 16) {
-    if (g.nqt > 1 && (g.nqt % 4) == 0) {
-      const long nb = (long)g.B * g.nwy * g.nwx * (g.nqt / 4) * g.heads;
-      hipLaunchKernelGGL((attn_fwd_mt_kernel<T, HD>), dim3((unsigned)nb), dim3(256), 0, st,
-                         (const T*)qkv, bias_t, (T*)out, lse, g);
-      return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
-    }
-  }
-  const long blocks = (long)g.B * g.nwy * g.nwx * g.nqt * (g.heads / NW);
-  hipLaunchKernelGGL((attn_fwd_kernel<T, HD, NW>), dim3((unsigned)blocks), dim3(NW * 64), 0, st,
-                     (const T*)qkv, bias_t, (T*)out, lse, g);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
-}
-
-// Grid of the persistent single-tile backward kernels: every workgroup ends with one flush of its bias-gradient table
-// (225 global atomics per wave onto the 2,700 floats of the 12 heads).  With 1024 x (heads / NW) workgroups that was
-// 2.7 M same-line device-scope atomics per launch - 0.2 ms, 40 % of the stage-1 launch (the loops themselves ran six
-// rounds of 0.05 ms).  Launch only as many workgroups as are resident at once and let them walk more windows.
-int bwd_persistent_grid(int nwin, int ngroups, int NW) {
-  const int resident = 256 * (NW == 4 ? 2 : (NW == 2 ? 2 : 4));     // CUs x workgroups per CU (launch bounds / LDS)
-  int gx = resident / (ngroups > 0 ? ngroups : 1);
-  if (gx < 1) gx = 1;
-  return nwin < gx ? nwin : gx;
-}
-
-template <typename T, int HD, int NW>
+// AB_FAST2 on the window-major operands; RC: q / k / v recomputed from the block's saved LN1 output
+template <typename T>
 int launch_bwd_wm(const void* qkvw, const float* bias_t, const void* dout, const float* lsew, void* dqkv,
                   float* dbias_t, const AttnGeo& g, hipStream_t st) {
-  if (g.heads % NW || g.nqt != 1 || g.ws != 8) return SODT_EINVAL;
+  constexpr int NW = attn_nw(DTYPE<T>, 16, true);
   const int nwin = g.B * g.nwy * g.nwx;
-  const int gx = bwd_persistent_grid(nwin, g.heads / NW, NW);
-  hipLaunchKernelGGL((attn_bwd_fast2_kernel<T, HD, NW, true>), dim3(gx, g.heads / NW), dim3(NW * 64), 0, st,
-                     (const T*)qkvw, bias_t, (const T*)dout, lsew, (T*)dqkv, dbias_t, g, nwin);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<attn_bwd_fast2_kernel<T, 16, NW, true>>(dim3(bwd_persistent_grid(nwin, g.heads / NW, NW), g.heads / NW), dim3(NW * 64), 0, st,
+                                                            (const T*)qkvw, bias_t, (const T*)dout, lsew, (T*)dqkv, dbias_t, g, nwin, (const unsigned char*)nullptr);
 }
 
-// the same walk with q / k / v recomputed from the block's saved LN1 output (RC)
 int launch_bwd_rc(const void* xn1, const unsigned char* wpk, const float* bias_t, const void* dout, const float* lsew, void* dqkv,
                   float* dbias_t, const AttnGeo& g, hipStream_t st) {
-  if (g.heads != 12 || g.C != 192 || g.nqt != 1 || g.ws != 8) return SODT_EINVAL;
   const int nwin = g.B * g.nwy * g.nwx;
-  int gx = bwd_persistent_grid(nwin, g.heads / 4, 4);
-  gx = gx >= 8 ? gx / 8 * 8 : 8;                      // walkers in whole rounds of the 8 XCDs (see the kernel's id map); walkers
-  //                                                    beyond the window count only join the final (all-zero) bias-gradient flush
-  hipLaunchKernelGGL((attn_bwd_fast2_kernel<bf16, 16, 4, true, true>), dim3(3 * gx), dim3(256), 0, st,
-                     (const bf16*)xn1, bias_t, (const bf16*)dout, lsew, (bf16*)dqkv, dbias_t, g, nwin, wpk);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<attn_bwd_fast2_kernel<bf16, 16, 4, true, true>>(dim3(3 * attn_rc_grid(nwin)), dim3(256), 0, st,
+                                                                     (const bf16*)xn1, bias_t, (const bf16*)dout, lsew, (bf16*)dqkv, dbias_t, g, nwin, wpk);
 }
 
-template <typename T, int HD, int NW>
-int launch_bwd(const void* qkv, const float* bias_t, const void* out, const void* dout, const float* lse, void* dqkv,
+template <typename T, int HD>
+int launch_bwd(AttnBwdKind kind, const void* qkv, const float* bias_t, const void* out, const void* dout, const float* lse, void* dqkv,
                float* dbias_t, float* scratch, const AttnGeo& g, hipStream_t st) {
-  if (g.heads % NW) return SODT_EINVAL;
+  constexpr int NW = attn_nw(DTYPE<T>, HD, true);
+  constexpr bool PFOK = (4 * Lay<T, HD>::DCH <= 16);
   const long M = (long)g.B * g.H * g.W;
-  const int nwin = g.B * g.nwy * g.nwx;
+  const int nwin = g.B * g.nwy * g.nwx, nitems = nwin * g.nqt;
+  const dim3 grid(nitems < 1024 ? nitems : 1024, g.heads / NW), block(NW * 64);
   float* dq_acc = nullptr; float* delta = nullptr;
-  if (g.nqt > 1) {
+  if (kind == AB_DKV_DQ || kind == AB_MT) {          // multi-tile windows: delta = rowsum(dO o O) first
     if (!scratch || !out) return SODT_EINVAL;
     dq_acc = scratch; delta = scratch + M * g.C;
-    hipLaunchKernelGGL((attn_delta_kernel<T>), dim3(1024), dim3(256), 0, st, (const T*)out, (const T*)dout, delta, M, g.C, g.heads);
+    if (int err = sodt_launch<attn_delta_kernel<T>>(dim3(1024), dim3(256), 0, st, (const T*)out, (const T*)dout, delta, M, g.C, g.heads)) return err;
   }
-  const int nitems = nwin * g.nqt;
-  int gx = nitems < 1024 ? nitems : 1024;
-  constexpr bool PFOK = (4 * Lay<T, HD>::DCH <= 16);
-  if (PFOK && g.nqt == 1 && g.ws == 8) {
-    gx = bwd_persistent_grid(nwin, g.heads / NW, NW);
-    if constexpr (PFOK) {
-      hipLaunchKernelGGL((attn_bwd_fast2_kernel<T, HD, NW>), dim3(gx, g.heads / NW), dim3(NW * 64), 0, st,
-                         (const T*)qkv, bias_t, (const T*)dout, lse, (T*)dqkv, dbias_t, g, nwin);
-    }
-  } else if (PFOK && g.nqt == 1) {
-    hipLaunchKernelGGL((attn_bwd_kernel<T, HD, NW, PFOK>), dim3(gx, g.heads / NW), dim3(NW * 64), 0, st,
-                       (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, dbias_t, dq_acc, g, nwin, 0);
-  } else {
-    if constexpr (HD % TT<T>::MMA_K == 0 && Lay<T, HD>::DCH >= 4 && Lay<T, HD>::DCH <= 16) {
-      if (g.nqt > 1 && g.shift == 0 && g.ws <= 32 && (g.nqt % 4) == 0 && (g.N % 128) == 0) {   // two passes, no dQ atomics
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD>), dim3((unsigned)(nwin * g.heads * (g.N / 128))), dim3(256), 0, st,
-                           (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, g);
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), dim3((unsigned)(nwin * g.heads * (g.N / 128))), dim3(256), 0, st,
-                           (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, dbias_t, g);
-        return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  switch (kind) {
+    case AB_FAST2:
+      if constexpr (PFOK)
+        return sodt_launch<attn_bwd_fast2_kernel<T, HD, NW>>(dim3(bwd_persistent_grid(nwin, g.heads / NW, NW), g.heads / NW), block, 0, st,
+                                                             (const T*)qkv, bias_t, (const T*)dout, lse, (T*)dqkv, dbias_t, g, nwin, (const unsigned char*)nullptr);
+      break;
+    case AB_SINGLE:      // no input selects it today (a single-tile window is 8x8, which AB_FAST2 takes); the instantiation stays
+      return sodt_launch<attn_bwd_kernel<T, HD, NW, PFOK>>(grid, block, 0, st, (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv,
+                                                           dbias_t, dq_acc, g, nwin, 0);
+    case AB_DKV_DQ:
+      if constexpr (attn_mt2_built(DTYPE<T>, HD)) {
+        const dim3 grid2((unsigned)(nwin * g.heads * (g.N / 128)));
+        if (int err = sodt_launch<attn_bwd_dkv_kernel<T, HD>>(grid2, dim3(256), 0, st, (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, g)) return err;
+        return sodt_launch<attn_bwd_dq_kernel<T, HD>>(grid2, dim3(256), 0, st, (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, dbias_t, g);
       }
-    }
-    if (g.nqt > 1) {
-      hipLaunchKernelGGL((attn_bwd_mt_kernel<T, HD, NW>), dim3(gx, g.heads / NW), dim3(NW * 64), 0, st,
-                         (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, dbias_t, dq_acc, g, nwin);
-      hipLaunchKernelGGL((attn_dq_finish_kernel<T>), dim3(1024), dim3(256), 0, st, dq_acc, (T*)dqkv, M, g.C);
-      return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
-    }
-    // multi-tile windows: keep the whole (2ws-1)^2 bias-gradient table of each head in LDS when it fits
-    using L = Lay<T, HD>;
-    const int L2 = 2 * g.ws - 1;
-    const int static_lds = NW * (4 * L::QTILE + 2 * L::STILE) + 2 * NW * 228 * 4 + 2 * NW * 64 * 4 + 2048;
-    const int dyn = NW * L2 * L2 * 4;
-    int fulldb = (g.nqt > 1 && static_lds + dyn <= 160 * 1024) ? 1 : 0;
-    if (fulldb) {
-      static int attr_bytes = 0;
-      if (dyn > attr_bytes) {
-        if (hipFuncSetAttribute((const void*)attn_bwd_kernel<T, HD, NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess) {
-          (void)hipGetLastError();
-          fulldb = 0;
-        } else attr_bytes = dyn;
-      }
-      if (gx > 128) gx = 128;      // few, long-lived workgroups: one table flush each
-    }
-    hipLaunchKernelGGL((attn_bwd_kernel<T, HD, NW, false>), dim3(gx, g.heads / NW), dim3(NW * 64), fulldb ? dyn : 0, st,
-                       (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv, dbias_t, dq_acc, g, nwin, fulldb);
+      break;
+    case AB_MT:
+      if (int err = sodt_launch<attn_bwd_mt_kernel<T, HD, NW>>(grid, block, 0, st, (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv,
+                                                               dbias_t, dq_acc, g, nwin)) return err;
+      return sodt_launch<attn_dq_finish_kernel<T>>(dim3(1024), dim3(256), 0, st, dq_acc, (T*)dqkv, M, g.C);
+    case AB_GENERIC:     // single-tile windows of the (T, HD) without register-resident fragments; its in-LDS bias-gradient table
+      //                    (fulldb) is for multi-tile windows, which AB_DKV_DQ / AB_MT take
+      return sodt_launch<attn_bwd_kernel<T, HD, NW, false>>(grid, block, 0, st, (const T*)qkv, bias_t, (const T*)dout, lse, delta, (T*)dqkv,
+                                                            dbias_t, dq_acc, g, nwin, 0);
   }
-  if (g.nqt > 1)
-    hipLaunchKernelGGL((attn_dq_finish_kernel<T>), dim3(1024), dim3(256), 0, st, dq_acc, (T*)dqkv, M, g.C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return SODT_EINVAL;
 }
 
 }  // namespace
@@ -2447,16 +2388,17 @@ extern "C" int sodt_window_attn_fwd(const void* qkv, const float* bias_t, void* 
   if (!qkv || !bias_t || !out || !make_geo(g, B, H, W, C, heads, ws, shift)) return SODT_EINVAL;
   hipStream_t st = (hipStream_t)st_;
   const int hd = C / heads;
+  const AttnRoute r = attn_fwd_route(dtype, hd, g);
+  if (!r.nw) return SODT_EINVAL;
+  const AttnFwdKind k = (AttnFwdKind)r.kind;
   if (dtype == SODT_BF16) {
-    if (hd == 16) return launch_fwd<bf16, 16, 4>(qkv, bias_t, out, lse, g, st);
-    if (hd == 32) return launch_fwd<bf16, 32, 4>(qkv, bias_t, out, lse, g, st);
-    if (hd == 64) return launch_fwd<bf16, 64, 2>(qkv, bias_t, out, lse, g, st);
-  } else if (dtype == SODT_F32) {
-    if (hd == 16) return launch_fwd<float, 16, 4>(qkv, bias_t, out, lse, g, st);
-    if (hd == 32) return launch_fwd<float, 32, 2>(qkv, bias_t, out, lse, g, st);
-    if (hd == 64) return launch_fwd<float, 64, 2>(qkv, bias_t, out, lse, g, st);
+    if (hd == 16) return launch_fwd<bf16, 16>(k, qkv, bias_t, out, lse, g, st);
+    if (hd == 32) return launch_fwd<bf16, 32>(k, qkv, bias_t, out, lse, g, st);
+    return launch_fwd<bf16, 64>(k, qkv, bias_t, out, lse, g, st);
   }
-  return SODT_EINVAL;
+  if (hd == 16) return launch_fwd<float, 16>(k, qkv, bias_t, out, lse, g, st);
+  if (hd == 32) return launch_fwd<float, 32>(k, qkv, bias_t, out, lse, g, st);
+  return launch_fwd<float, 64>(k, qkv, bias_t, out, lse, g, st);
 }
 
 extern "C" int sodt_window_attn_bwd(const void* qkv, const float* bias_t, const void* out, const void* dout,
@@ -2467,16 +2409,17 @@ extern "C" int sodt_window_attn_bwd(const void* qkv, const float* bias_t, const 
   if (!qkv || !bias_t || !dout || !lse || !dqkv || !dbias_t || !make_geo(g, B, H, W, C, heads, ws, shift)) return SODT_EINVAL;
   hipStream_t st = (hipStream_t)st_;
   const int hd = C / heads;
+  const AttnRoute r = attn_bwd_route(dtype, hd, g);
+  if (!r.nw) return SODT_EINVAL;
+  const AttnBwdKind k = (AttnBwdKind)r.kind;
   if (dtype == SODT_BF16) {
-    if (hd == 16) return launch_bwd<bf16, 16, 4>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
-    if (hd == 32) return launch_bwd<bf16, 32, 2>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
-    if (hd == 64) return launch_bwd<bf16, 64, 1>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
-  } else if (dtype == SODT_F32) {
-    if (hd == 16) return launch_bwd<float, 16, 2>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
-    if (hd == 32) return launch_bwd<float, 32, 2>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
-    if (hd == 64) return launch_bwd<float, 64, 1>(qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
+    if (hd == 16) return launch_bwd<bf16, 16>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
+    if (hd == 32) return launch_bwd<bf16, 32>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
+    return launch_bwd<bf16, 64>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
   }
-  return SODT_EINVAL;
+  if (hd == 16) return launch_bwd<float, 16>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
+  if (hd == 32) return launch_bwd<float, 32>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
+  return launch_bwd<float, 64>(k, qkv, bias_t, out, dout, lse, dqkv, dbias_t, dq_acc, g, st);
 }
 
 /* the same backward on the window-major q / k / v and log-sum-exp the fused forward saves (wmsa_block.hip) */
@@ -2486,11 +2429,9 @@ extern "C" int sodt_window_attn_bwd_wm(const void* qkvw, const float* bias_t, co
   AttnGeo g;
   if (!qkvw || !bias_t || !dout || !lsew || !dqkv || !dbias_t || !make_geo(g, B, H, W, C, heads, ws, shift)) return SODT_EINVAL;
   hipStream_t st = (hipStream_t)st_;
-  const int hd = C / heads;
-  if (hd != 16) return SODT_EINVAL;
-  if (dtype == SODT_BF16) return launch_bwd_wm<bf16, 16, 4>(qkvw, bias_t, dout, lsew, dqkv, dbias_t, g, st);
-  if (dtype == SODT_F32) return launch_bwd_wm<float, 16, 2>(qkvw, bias_t, dout, lsew, dqkv, dbias_t, g, st);
-  return SODT_EINVAL;
+  if (!attn_bwd_wm_route(dtype, C / heads, g).nw) return SODT_EINVAL;
+  return dtype == SODT_BF16 ? launch_bwd_wm<bf16>(qkvw, bias_t, dout, lsew, dqkv, dbias_t, g, st)
+                            : launch_bwd_wm<float>(qkvw, bias_t, dout, lsew, dqkv, dbias_t, g, st);
 }
 
 /* First stage of the fused W-MSA block's backward (bf16, C = 192, 12 heads, 8x8 windows): d(attention output) -> dqkv and the
@@ -2502,6 +2443,6 @@ extern "C" int sodt_wmsa_block_bwd(const void* xn1, const void* wpk, const float
                                    int dtype, sodt_stream_t st_) {
   AttnGeo g;
   if (!xn1 || !wpk || !bias_t || !dout || !lsew || !dqkv || !dbias_t || !make_geo(g, B, H, W, C, heads, ws, shift)) return SODT_EINVAL;
-  if (dtype != SODT_BF16) return SODT_EINVAL;            // the f32 parity path keeps its saved q / k / v (sodt_window_attn_bwd_wm)
+  if (!attn_bwd_rc_route(dtype, g).nw) return SODT_EINVAL;      // (the f32 parity path keeps its saved q / k / v: sodt_window_attn_bwd_wm)
   return launch_bwd_rc(xn1, (const unsigned char*)wpk, bias_t, dout, lsew, dqkv, dbias_t, g, (hipStream_t)st_);
 }

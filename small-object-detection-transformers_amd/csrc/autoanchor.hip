@@ -12,6 +12,7 @@
 //   * no block waits on another block, no cooperative launch, no host read inside an entry.
 // Anchor sets live in LDS; each thread keeps its label in registers and walks the set.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -266,12 +267,11 @@ extern "C" int sodt_anchor_stats(const float* wh, long N, const float* sets, int
   if (((uintptr_t)wh & 7) || ((uintptr_t)sets & 3) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 15) || ws_bytes < need)
     return SODT_EINVAL;
   hipStream_t s = (hipStream_t)st;
-  if (hipMemsetAsync(ws, 0, tickets_bytes(S), s) != hipSuccess) return SODT_EINVAL;
+  if (hipMemsetAsync(ws, 0, tickets_bytes(S), s) != hipSuccess) return SODT_ELAUNCH;
   unsigned* ticket = (unsigned*)ws;
   Slot* part = (Slot*)((char*)ws + tickets_bytes(S));
-  hipLaunchKernelGGL(anchor_stats_kernel, dim3(blocks_for(N, NT), S), dim3(NT), 0, s, (const float2*)wh, N, sets, n, thr,
+  return sodt_launch<anchor_stats_kernel>(dim3(blocks_for(N, NT), S), dim3(NT), 0, s, (const float2*)wh, N, sets, n, thr,
                      ticket, part, out);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_anchor_evolve_workspace_bytes(long N, size_t* bytes) {
@@ -290,14 +290,14 @@ extern "C" int sodt_anchor_evolve(const float* wh, long N, float thr, double* k,
     return SODT_EINVAL;
   if (G == 0) return SODT_OK;
   hipStream_t s = (hipStream_t)st;
-  if (hipMemsetAsync(ws, 0, 16, s) != hipSuccess) return SODT_EINVAL;
+  if (hipMemsetAsync(ws, 0, 16, s) != hipSuccess) return SODT_ELAUNCH;
   unsigned* ticket = (unsigned*)ws;
   double* part = (double*)((char*)ws + 16);
   const dim3 grid(blocks_for(N, NT));
   for (int g = 0; g < G; ++g)
-    hipLaunchKernelGGL(anchor_evolve_kernel, grid, dim3(NT), 0, s, (const float2*)wh, N, thr, n, k, f, v + (size_t)g * 2 * n,
-                       ticket, part, accepted ? accepted + g : (int*)nullptr);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    if (int err = sodt_launch<anchor_evolve_kernel>(grid, dim3(NT), 0, s, (const float2*)wh, N, thr, n, k, f, v + (size_t)g * 2 * n,
+                                                   ticket, part, accepted ? accepted + g : (int*)nullptr)) return err;
+  return SODT_OK;
 }
 
 extern "C" int sodt_kmeans_lloyd_workspace_bytes(long N, int R, int n, size_t* bytes) {
@@ -316,13 +316,13 @@ extern "C" int sodt_kmeans_lloyd(const double* obs, long N, double* books, int* 
     return SODT_EINVAL;
   if (iters == 0) return SODT_OK;
   hipStream_t s = (hipStream_t)st;
-  if (hipMemsetAsync(ws, 0, tickets_bytes(R), s) != hipSuccess) return SODT_EINVAL;
+  if (hipMemsetAsync(ws, 0, tickets_bytes(R), s) != hipSuccess) return SODT_ELAUNCH;
   unsigned* ticket = (unsigned*)ws;
   double* part = (double*)((char*)ws + tickets_bytes(R));
   const dim3 grid(blocks_for(N, 64), R);
   const size_t lds = sizeof(double) * 3 * (size_t)n * 64;           // at most 48 KiB (n = 32)
   for (int it = 0; it < iters; ++it)
-    hipLaunchKernelGGL(kmeans_lloyd_kernel, grid, dim3(64), lds, s, (const double2*)obs, N, books, alive, prev, done, n,
-                       thresh, ticket, part);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    if (int err = sodt_launch<kmeans_lloyd_kernel>(grid, dim3(64), (int)lds, s, (const double2*)obs, N, books, alive, prev, done, n,
+                                                  thresh, ticket, part)) return err;
+  return SODT_OK;
 }

@@ -11,6 +11,7 @@
 // head_dim = 4 is far below any MFMA shape, so this is VALU work: one thread per (token, pair), looping over
 // the <= 64 keys of its window and the 12 heads.  e is kept in f32 (workspace of B*t*t*192 floats).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -273,8 +274,7 @@ extern "C" int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_
   CaGeo g;
   if (!rgb || !ir || !w || !b || !e || !ca_geo(g, B, S, 1, 0, ir_bstride)) return SODT_EINVAL;
   const long ntok = (long)B * g.t * g.t;
-  hipLaunchKernelGGL(patch_embed4_fwd_kernel, dim3((unsigned)((ntok * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, e, g, ntok);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<patch_embed4_fwd_kernel>(dim3((unsigned)((ntok * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, e, g, ntok);
 }
 
 extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
@@ -283,8 +283,7 @@ extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_
   if (!rgb || !ir || !de || !dw || !db || !ca_geo(g, B, S, 1, 0, ir_bstride)) return SODT_EINVAL;
   const long ntok = (long)B * g.t * g.t;
   const unsigned gy = (unsigned)(ntok < 512 ? ntok : 512);
-  hipLaunchKernelGGL(patch_embed4_bwd_kernel, dim3((4 * CE * 17 + 255) / 256, gy), dim3(256), 0, (hipStream_t)st, rgb, ir, de, dw, db, g, ntok);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<patch_embed4_bwd_kernel>(dim3((4 * CE * 17 + 255) / 256, gy), dim3(256), 0, (hipStream_t)st, rgb, ir, de, dw, db, g, ntok);
 }
 
 extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int S, int ws,
@@ -293,10 +292,9 @@ extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const 
   if (!e || !gamma || !beta || !out || !ca_geo(g, B, S, ws, shift, 0)) return SODT_EINVAL;
   const long ntok = (long)B * g.t * g.t;
   const unsigned gr = (unsigned)((ntok * 4 + 127) / 128);
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(cross_attn_ln_fwd_kernel<bf16>, dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (bf16*)out, g, ntok);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(cross_attn_ln_fwd_kernel<float>, dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (float*)out, g, ntok);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<cross_attn_ln_fwd_kernel<bf16>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (bf16*)out, g, ntok);
+  if (dtype == SODT_F32) return sodt_launch<cross_attn_ln_fwd_kernel<float>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (float*)out, g, ntok);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
@@ -305,8 +303,7 @@ extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const 
   if (!e || !gamma || !dout || !de || !dgamma || !dbeta || !ca_geo(g, B, S, ws, shift, 0)) return SODT_EINVAL;
   const long ntok = (long)B * g.t * g.t;
   const unsigned gr = (unsigned)((ntok * 4 + 127) / 128);
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(cross_attn_ln_bwd_kernel<bf16>, dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const bf16*)dout, de, dgamma, dbeta, g, ntok);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(cross_attn_ln_bwd_kernel<float>, dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const float*)dout, de, dgamma, dbeta, g, ntok);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<cross_attn_ln_bwd_kernel<bf16>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const bf16*)dout, de, dgamma, dbeta, g, ntok);
+  if (dtype == SODT_F32) return sodt_launch<cross_attn_ln_bwd_kernel<float>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const float*)dout, de, dgamma, dbeta, g, ntok);
+  return SODT_EINVAL;
 }

@@ -19,9 +19,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-#define SODT_OK 0
-#define SODT_EINVAL 1
-
 template <typename T> struct TT;
 template <> struct TT<float> {
   static constexpr int KPL = 4;     // elements per 16-byte chunk

@@ -21,6 +21,7 @@
 // The forward can store the (B, cout, H, W) float32 output of the branch directly, the gradients can read the float32 gradient planes
 // (deeplabedsr.py:73).  bf16 only (the float32 parity path keeps the K-segment GEMM).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -714,15 +715,13 @@ int sodt_conv3x3_c64n8_fwd(const void* x, const void* w, const float* bias, void
                            hipStream_t st) {
   if (!ok_common(x, w, y_nchw ? (const void*)y_nchw : y, B, H, W, dtype) || (((uintptr_t)bias) & 15) || cout < 1 || cout > 8) return SODT_EINVAL;
   const Tiles t = make_tiles(B, H, W, F_TH);
-  hipLaunchKernelGGL(conv3_n8_fwd_kernel, dim3(GRID), dim3(256), 0, st, (const bf16*)x, (const bf16*)w, bias, (bf16*)y, t, y_nchw, cout);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<conv3_n8_fwd_kernel>(dim3(GRID), dim3(256), 0, st, (const bf16*)x, (const bf16*)w, bias, (bf16*)y, t, y_nchw, cout);
 }
 
 int sodt_conv3x3_c64n8_dgrad(const void* dy, const float* dy_nchw, const void* wT, void* dx, int B, int H, int W, int cout, int dtype, hipStream_t st) {
   if (!ok_common(dy_nchw ? (const void*)dy_nchw : dy, wT, dx, B, H, W, dtype) || cout < 1 || cout > 8 || (dy_nchw && cout > 4)) return SODT_EINVAL;
   const Tiles t = make_tiles(B, H, W, D_TH);
-  hipLaunchKernelGGL(conv3_n8_dgrad_kernel, dim3(GRID), dim3(256), 0, st, (const bf16*)dy, (const bf16*)wT, (bf16*)dx, t, dy_nchw, cout);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<conv3_n8_dgrad_kernel>(dim3(GRID), dim3(256), 0, st, (const bf16*)dy, (const bf16*)wT, (bf16*)dx, t, dy_nchw, cout);
 }
 
 long sodt_conv3x3_c64n8_wgrad_scratch_bytes(void) { return (long)GRID * W_PART * 4; }
@@ -732,9 +731,8 @@ int sodt_conv3x3_c64n8_wgrad(const void* dy, const float* dy_nchw, const void* x
   if (!ok_common(dy_nchw ? (const void*)dy_nchw : dy, x, scratch, B, H, W, dtype) || !dw || cout < 1 || cout > 8 || (dy_nchw && cout > 4))
     return SODT_EINVAL;
   const Tiles t = make_tiles(B, H, W, W_TH);
-  hipLaunchKernelGGL(conv3_n8_wgrad_kernel, dim3(GRID), dim3(256), 0, st, (const bf16*)dy, (const bf16*)x, scratch, t, dy_nchw, cout);
-  hipLaunchKernelGGL(conv3_n8_wgrad_reduce_kernel, dim3((cout * 577 + 255) / 256), dim3(256), 0, st, (const float*)scratch, GRID, dw, db, cout);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (int err = sodt_launch<conv3_n8_wgrad_kernel>(dim3(GRID), dim3(256), 0, st, (const bf16*)dy, (const bf16*)x, scratch, t, dy_nchw, cout)) return err;
+  return sodt_launch<conv3_n8_wgrad_reduce_kernel>(dim3((cout * 577 + 255) / 256), dim3(256), 0, st, (const float*)scratch, GRID, dw, db, cout);
 }
 
 int sodt_conv3x3_c64_fwd(const void* x, const void* w, const float* bias, const void* resid, const void* aux, void* y, int B, int H, int W,
@@ -752,8 +750,7 @@ int sodt_conv3x3_c64_fwd(const void* x, const void* w, const float* bias, const 
   if ((long)B * H * W * a.im * a.im >= (1L << 31) || (long)B * H * W * a.om * a.om >= (1L << 31)) return SODT_EINVAL;
   const Tiles t = make_tiles(B, H, W, C_TH);
   const int grid = (int)(t.ntiles < GRID / 2 ? ((t.ntiles + 7) / 8) * 8 : GRID / 2);       // one 8-wave workgroup per CU
-  hipLaunchKernelGGL(conv3_c64_kernel, dim3(grid), dim3(512), 0, st, a, t);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<conv3_c64_kernel>(dim3(grid), dim3(512), 0, st, a, t);
 }
 
 long sodt_conv3x3_c64_wgrad_scratch_bytes(void) { return (long)(GRID / 2) * G_PART * 4; }
@@ -766,11 +763,10 @@ int sodt_conv3x3_c64_wgrad(const void* dy, const void* x, float* dw, float* db, 
   if ((long)B * H * W * dm * dm >= (1L << 31)) return SODT_EINVAL;
   const Tiles t = make_tiles(B, H, W, G_TH);
   const int grid = (int)(t.ntiles < GRID / 2 ? ((t.ntiles + 7) / 8) * 8 : GRID / 2);       // one 8-wave workgroup per CU
-  hipLaunchKernelGGL(conv3_c64_wgrad_kernel, dim3(grid), dim3(512), 0, st, (const bf16*)dy, (const bf16*)x, scratch, t, dm, geo ? geo->out_i : 0,
-                     geo ? geo->out_j : 0);
-  hipLaunchKernelGGL(conv3_c64_wgrad_reduce_kernel, dim3((G_PART + 63) / 64), dim3(256), 0, st, (const float*)scratch, grid, dw, db,
+  if (int err = sodt_launch<conv3_c64_wgrad_kernel>(dim3(grid), dim3(512), 0, st, (const bf16*)dy, (const bf16*)x, scratch, t, dm, geo ? geo->out_i : 0,
+                     geo ? geo->out_j : 0)) return err;
+  return sodt_launch<conv3_c64_wgrad_reduce_kernel>(dim3((G_PART + 63) / 64), dim3(256), 0, st, (const float*)scratch, grid, dw, db,
                      geo ? geo->w_row_stride : 1, geo ? geo->w_row_off : 0);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 }  // extern "C"

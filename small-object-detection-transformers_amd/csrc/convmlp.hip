@@ -20,6 +20,7 @@
 // f32 masters.  weff bf16 [C][4 C]: column tap * C + ci (the K order of the tap segments); weffT bf16 [C][4 C]: row ci, column
 // tap * C + co (the W operand of the input-gradient GEMM over the negated taps).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -246,26 +247,23 @@ extern "C" int sodt_convmlp_compose(const float* fc1_w, const float* fc1_b, cons
   if (!fc1_w || !fc1_b || !conv_w || !conv_b || !weff || !weffT || !beff || !vtap || C <= 0 || (C % 64) || dtype != SODT_BF16 ||
       (((uintptr_t)conv_w) & 15))
     return SODT_EINVAL;
-  hipLaunchKernelGGL(convmlp_compose_kernel, dim3(C / 32, C / 64 + 1, 4), dim3(256), 0, (hipStream_t)st, fc1_w, fc1_b, conv_w, conv_b,
+  return sodt_launch<convmlp_compose_kernel>(dim3(C / 32, C / 64 + 1, 4), dim3(256), 0, (hipStream_t)st, fc1_w, fc1_b, conv_w, conv_b,
                      (bf16*)weff, (bf16*)weffT, beff, vtap, C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_convmlp_border_fix(void* cp, void* ca, const float* vtap, int B, int H, int W, int C, int dtype, sodt_stream_t st) {
   if (!cp || !ca || !vtap || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || dtype != SODT_BF16 ||
       ((((uintptr_t)cp) | ((uintptr_t)ca)) & 15))
     return SODT_EINVAL;
-  hipLaunchKernelGGL(convmlp_border_fix_kernel, dim3(nblk((long)B * (H + W - 1) * (C / 8))), dim3(256), 0, (hipStream_t)st, (bf16*)cp,
+  return sodt_launch<convmlp_border_fix_kernel>(dim3(nblk((long)B * (H + W - 1) * (C / 8))), dim3(256), 0, (hipStream_t)st, (bf16*)cp,
                      (bf16*)ca, vtap, B, H, W, C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_convmlp_border_sums(const void* dc, float* bs, int B, int H, int W, int C, int dtype, sodt_stream_t st) {
   if (!dc || !bs || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || C > 384 || dtype != SODT_BF16 || B > 65535 || (((uintptr_t)dc) & 15))
     return SODT_EINVAL;
   const int len = H > W ? H : W;
-  hipLaunchKernelGGL(convmlp_border_sums_kernel, dim3((len + 7) / 8, B, 2), dim3(256), 0, (hipStream_t)st, (const bf16*)dc, bs, B, H, W, C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<convmlp_border_sums_kernel>(dim3((len + 7) / 8, B, 2), dim3(256), 0, (hipStream_t)st, (const bf16*)dc, bs, B, H, W, C);
 }
 
 extern "C" int sodt_convmlp_decompose(const float* dweff, const float* colsum, const float* bs, const float* fc1_w, const float* fc1_b,
@@ -275,7 +273,6 @@ extern "C" int sodt_convmlp_decompose(const float* dweff, const float* colsum, c
       C > CONVMLP_MAXC || ((((uintptr_t)conv_w) | ((uintptr_t)g_conv_w)) & 15))
     return SODT_EINVAL;
   const int n = (C / 64) * (C / 64);
-  hipLaunchKernelGGL(convmlp_decompose_kernel, dim3(8 * n + C / 32), dim3(256), 0, (hipStream_t)st, dweff, colsum, bs, fc1_w, fc1_b, conv_w,
+  return sodt_launch<convmlp_decompose_kernel>(dim3(8 * n + C / 32), dim3(256), 0, (hipStream_t)st, dweff, colsum, bs, fc1_w, fc1_b, conv_w,
                      g_conv_w, g_conv_b, g_fc1_w, g_fc1_b, C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }

@@ -16,6 +16,7 @@
 // the image instead of saving them and reduces the parameter gradients over a
 // grid-stride loop before a final burst of atomics.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -374,11 +375,10 @@ extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstr
   const long ntok = (long)B * g.t * g.t;
   const unsigned blocks = (unsigned)((ntok + 63) / 64);
   if (dtype == SODT_BF16)
-    hipLaunchKernelGGL(frontend_fwd_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, gamma, beta, (bf16*)out, g, ntok);
-  else if (dtype == SODT_F32)
-    hipLaunchKernelGGL(frontend_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, gamma, beta, (float*)out, g, ntok);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    return sodt_launch<frontend_fwd_kernel<bf16>>(dim3(blocks), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, gamma, beta, (bf16*)out, g, ntok);
+  if (dtype == SODT_F32)
+    return sodt_launch<frontend_fwd_kernel<float>>(dim3(blocks), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, gamma, beta, (float*)out, g, ntok);
+  return SODT_EINVAL;
 }
 
 extern "C" long sodt_frontend_bwd_workspace_bytes(int B, int S) {
@@ -403,13 +403,12 @@ extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstr
   const int cap = two_stage ? FE_BWD_GRID : FE_BWD_GRID / 2;
   const unsigned blocks = (unsigned)(nblk < cap ? nblk : cap);
   hipStream_t s = (hipStream_t)st;
-#define FE_BWD_LAUNCH(T_, WS_) hipLaunchKernelGGL((frontend_bwd_kernel<T_, WS_>), dim3(blocks), dim3(256), 0, s, rgb, ir, w, b, gamma, \
+#define FE_BWD_LAUNCH(T_, WS_) sodt_launch<frontend_bwd_kernel<T_, WS_>>(dim3(blocks), dim3(256), 0, s, rgb, ir, w, b, gamma, \
                                                   (const T_*)dout, dw, db, dgamma, dbeta, ws, g, ntok, nblk)
-  if (dtype == SODT_BF16) { if (two_stage) FE_BWD_LAUNCH(bf16, true); else FE_BWD_LAUNCH(bf16, false); }
-  else { if (two_stage) FE_BWD_LAUNCH(float, true); else FE_BWD_LAUNCH(float, false); }
+  const int rc = dtype == SODT_BF16 ? (two_stage ? FE_BWD_LAUNCH(bf16, true) : FE_BWD_LAUNCH(bf16, false))
+                                    : (two_stage ? FE_BWD_LAUNCH(float, true) : FE_BWD_LAUNCH(float, false));
 #undef FE_BWD_LAUNCH
-  if (two_stage)
-    hipLaunchKernelGGL(frontend_bwd_reduce_kernel, dim3(FE_PART / 64, (blocks + FE_RG - 1) / FE_RG), dim3(64), 0, s, ws, (int)blocks,
-                       dw, db, dgamma, dbeta);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (rc || !two_stage) return rc;
+  return sodt_launch<frontend_bwd_reduce_kernel>(dim3(FE_PART / 64, (blocks + FE_RG - 1) / FE_RG), dim3(64), 0, s, ws, (int)blocks,
+                                                 dw, db, dgamma, dbeta);
 }

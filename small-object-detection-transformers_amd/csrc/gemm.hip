@@ -14,15 +14,15 @@
 // (padded rows) so that the epilogue reads/writes whole 16-byte row chunks.
 // Roofline: MFMA for K >= 384; at K = 192 (stage 1) it is HBM-bound.
 #include "gemm_epi.h"
+#include "launch.h"
+#include "routes.h"
 
-bool sodt_nt3_eligible(const sodt_gemm_args* g);            // gemm3.hip: pipelined bf16 kernel for K >= 384
-int sodt_nt3_launch(const sodt_gemm_args* g, hipStream_t st);
-int sodt_tn3_launch(const sodt_gemm_tn_args* g, hipStream_t st);   // gemm3.hip: pipelined bf16 weight-gradient kernel
+int sodt_nt3_launch(const sodt_gemm_args* g, const NtRoute& r, hipStream_t st);      // gemm3.hip: pipelined bf16 kernel for K >= 384
+int sodt_tn3_launch(const sodt_gemm_tn_args* g, const TnRoute& r, hipStream_t st);   // gemm3.hip: pipelined bf16 weight-gradient kernel
 
 namespace {
 
-int g_force_tiled = 0;   // test hook: sodt_gemm_set_variant(1) forces the K-loop / 128x128 TN kernels, (2) the A-stationary NT kernel
-int g_variant = 0;
+int g_variant = SODT_VARIANT_AUTO;   // test hook: sodt_gemm_set_variant
 
 constexpr int BM = 128, BN = 128, ROWB = 128;          // ROWB: bytes per LDS row per K-step
 constexpr int STAGE_BYTES = BM * ROWB;                 // 16 KiB per operand per stage
@@ -370,15 +370,8 @@ int launch_as(const sodt_gemm_args* g, hipStream_t st) {
   const int KB = g->K * (int)sizeof(T);
   const int wbytes = BN_ * KB, sbytes = AS_BM * (BN_ + 4) * 4;
   const int lds = AS_BM * KB + (wbytes > sbytes ? wbytes : sbytes);
-  static int max_set = 0;
-  if (lds > max_set) {
-    if (hipFuncSetAttribute((const void*)gemm_as_kernel<T, BN_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
-      return SODT_EINVAL;
-    max_set = 160 * 1024;
-  }
   const long blocks = ((long)g->M + AS_BM - 1) / AS_BM;
-  hipLaunchKernelGGL((gemm_as_kernel<T, BN_>), dim3((unsigned)blocks), dim3(256), lds, st, *g);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<gemm_as_kernel<T, BN_>>(dim3((unsigned)blocks), dim3(256), lds, st, *g);
 }
 
 // ---------------------------------------------------------------------------------
@@ -614,12 +607,6 @@ template <typename T, int BN_, bool STATS, int CF, bool SIMPLE>
 int launch_bs(const sodt_gemm_args* g, hipStream_t st) {
   const int KB = g->K * (int)sizeof(T);
   const int lds = (BN_ + AS_BM) * KB;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_bs_kernel<T, BN_, STATS, CF, SIMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-      return SODT_EINVAL;
-    attr_set = true;
-  }
   const int ntiles = (g->N + BN_ - 1) / BN_;
   const long nrb = ((long)g->M + AS_BM - 1) / AS_BM;
   const int per_cu = lds <= 76 * 1024 ? 2 : 1;
@@ -628,8 +615,7 @@ int launch_bs(const sodt_gemm_args* g, hipStream_t st) {
   const long max_teams = (nrb + 7) / 8;
   if (teams_per_xcd > max_teams) teams_per_xcd = (int)max_teams;
   const int blocks = teams_per_xcd * ntiles * 8;
-  hipLaunchKernelGGL((gemm_bs_kernel<T, BN_, STATS, CF, SIMPLE>), dim3(blocks), dim3(256), lds, st, *g, teams_per_xcd);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<gemm_bs_kernel<T, BN_, STATS, CF, SIMPLE>>(dim3(blocks), dim3(256), lds, st, *g, teams_per_xcd);
 }
 
 // ---------------------------------------------------------------------------------
@@ -980,15 +966,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn2_kernel(const sodt_gemm_tn_arg
 template <typename T>
 int launch_tn2(const sodt_gemm_tn_args* g, hipStream_t st) {
   constexpr int lds = 2 * TN2Geo<T>::BMS * (TN2Geo<T>::YROW + TN2Geo<T>::XROW);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_tn2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-      return SODT_EINVAL;
-    attr_set = true;
-  }
   const int tiles = ((g->N + 255) / 256) * ((g->K + 191) / 192);
-  hipLaunchKernelGGL((gemm_tn2_kernel<T>), dim3(tiles * g->splits), dim3(512), lds, st, *g);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<gemm_tn2_kernel<T>>(dim3(tiles * g->splits), dim3(512), lds, st, *g);
 }
 
 bool aspec_ok(const sodt_aspec& a, int K, int kpl) {
@@ -1004,27 +983,46 @@ bool aspec_ok(const sodt_aspec& a, int K, int kpl) {
   return tot == K;
 }
 
-}  // namespace
+// the flag sets with a branch-free instantiation (nt_static_cf in routes.h); everything else is generic
+#define NT_STATIC_CF(X) \
+  X(0) X(SODT_EPI_BIAS) X(SODT_EPI_RESID) X(SODT_EPI_BIAS | SODT_EPI_RESID) X(SODT_EPI_BIAS | SODT_EPI_GELU_DUAL) X(SODT_EPI_DGELU)
 
-// branch-free instantiations for the flag sets the model's plain-tensor GEMMs use; everything else is generic
 template <typename T>
-int dispatch_bs(const sodt_gemm_args* g, bool simple, hipStream_t st) {
-  if (simple) {
-    switch (g->flags) {
-      case 0: return launch_bs<T, 128, false, 0, true>(g, st);
-      case SODT_EPI_BIAS: return launch_bs<T, 128, false, SODT_EPI_BIAS, true>(g, st);
-      case SODT_EPI_RESID: return launch_bs<T, 128, false, SODT_EPI_RESID, true>(g, st);
-      case SODT_EPI_BIAS | SODT_EPI_RESID: return launch_bs<T, 128, false, SODT_EPI_BIAS | SODT_EPI_RESID, true>(g, st);
-      case SODT_EPI_BIAS | SODT_EPI_GELU_DUAL: return launch_bs<T, 128, false, SODT_EPI_BIAS | SODT_EPI_GELU_DUAL, true>(g, st);
-      case SODT_EPI_DGELU: return launch_bs<T, 128, false, SODT_EPI_DGELU, true>(g, st);
-      default: break;
+int launch_nt(const sodt_gemm_args* g, const NtRoute& r, hipStream_t st) {
+  switch (r.kind) {
+    case NT_REFUSED: return SODT_EINVAL;
+    case NT_PIPE: return sodt_nt3_launch(g, r, st);
+    case NT_BS_STATS: return launch_bs<T, 128, true, -1, false>(g, st);
+    case NT_BS_SIMPLE:
+      switch (r.cf) {
+#define X(F) case F: return launch_bs<T, 128, false, F, true>(g, st);
+        NT_STATIC_CF(X)
+#undef X
+      }
+      return SODT_EINVAL;
+    case NT_BS_GENERIC: return launch_bs<T, 128, false, -1, false>(g, st);
+    case NT_AS128: return launch_as<T, 128>(g, st);
+    case NT_AS64: return launch_as<T, 64>(g, st);     // no input selects it today (nt_route); the instantiation stays
+    case NT_TILED: {
+      const long tiles = ((long)(g->M + BM - 1) / BM) * ((g->N + BN - 1) / BN);
+      if (tiles > 0x7fffffffL) return SODT_EINVAL;
+      const dim3 grid((unsigned)tiles), block(256);
+      switch (r.cf) {
+#define X(F) case F: return sodt_launch<gemm_nt_kernel<T, F>>(grid, block, 0, st, *g);
+        NT_STATIC_CF(X)
+#undef X
+      }
+      return sodt_launch<gemm_nt_kernel<T, -1>>(grid, block, 0, st, *g);
     }
   }
-  return launch_bs<T, 128, false, -1, false>(g, st);
+  return SODT_EINVAL;
 }
+#undef NT_STATIC_CF
+
+}  // namespace
 
 extern "C" int sodt_gemm_nt(const sodt_gemm_args* g, int dtype, sodt_stream_t st) {
-  if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0) return SODT_EINVAL;
+  if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0 || (dtype != SODT_BF16 && dtype != SODT_F32)) return SODT_EINVAL;
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!aspec_ok(g->a, g->K, kpl)) return SODT_EINVAL;
   if ((g->ldw % kpl) || (((uintptr_t)g->W) & 15) || !g->C) return SODT_EINVAL;
@@ -1040,78 +1038,31 @@ extern "C" int sodt_gemm_nt(const sodt_gemm_args* g, int dtype, sodt_stream_t st
   if ((g->flags & SODT_EPI_STATS) && !g->stats) return SODT_EINVAL;
   if ((g->flags & SODT_EPI_AFFINE_SILU) && (!g->scale || !g->shift || ((((uintptr_t)g->scale) | ((uintptr_t)g->shift)) & 15))) return SODT_EINVAL;
   if (g->oscatter && !g->a.spatial) return SODT_EINVAL;
-  if ((g->flags & SODT_EPI_DGELU_RC) && !(dtype == SODT_BF16 && sodt_nt3_eligible(g))) return SODT_EINVAL;
-  if (dtype == SODT_BF16 && (g_variant == 0 || g_variant == 3) && sodt_nt3_eligible(g)) return sodt_nt3_launch(g, (hipStream_t)st);
-  // short contraction -> A-stationary kernel (row bytes a multiple of 128 so the XOR swizzle stays in-row)
-  {
-    const int es = dtype == SODT_BF16 ? 2 : 4;
-    const int KB = g->K * es;
-    bool seg_ok = true;
-    for (int i = 0; i < g->a.nseg; ++i) seg_ok = seg_ok && ((g->a.s[i].klen * es) % 16 == 0);
-    if (!(g->flags & SODT_EPI_DETECT) && (KB % 128) == 0 && KB <= 384 && seg_ok && !g_force_tiled) {
-      hipStream_t s_ = (hipStream_t)st;
-      const int kplv = dtype == SODT_BF16 ? 8 : 4;
-      // (that kernel adds the residual before the generic epilogue: a ReLU / ReLU mask must come first, so not with both)
-      const bool relu_resid = (g->flags & (SODT_EPI_RELU | SODT_EPI_DRELU)) && (g->flags & SODT_EPI_RESID);
-      const bool bs_ok = (g->N % kplv) == 0 && (g->flags & SODT_EPI_OUT_F32) == 0 && g_variant != 2 && !relu_resid;
-      if (bs_ok) {
-        const bool stt = (g->flags & SODT_EPI_STATS) != 0;
-        const bool simple = g->a.nseg == 1 && !g->a.spatial && !g->oscatter;
-        if (dtype == SODT_BF16) return stt ? launch_bs<bf16, 128, true, -1, false>(g, s_) : dispatch_bs<bf16>(g, simple, s_);
-        if (dtype == SODT_F32) return stt ? launch_bs<float, 128, true, -1, false>(g, s_) : dispatch_bs<float>(g, simple, s_);
-        return SODT_EINVAL;
-      }
-      if (dtype == SODT_BF16) return KB <= 384 ? launch_as<bf16, 128>(g, s_) : launch_as<bf16, 64>(g, s_);
-      if (dtype == SODT_F32) return KB <= 384 ? launch_as<float, 128>(g, s_) : launch_as<float, 64>(g, s_);
-      return SODT_EINVAL;
-    }
-  }
-  if (dtype == SODT_BF16 && (g_variant == 0 || g_variant == 3) && sodt_nt3_eligible(g)) return sodt_nt3_launch(g, (hipStream_t)st);
-  const long tiles = ((long)(g->M + BM - 1) / BM) * ((g->N + BN - 1) / BN);
-  if (tiles > 0x7fffffffL) return SODT_EINVAL;
-  dim3 grid((unsigned)tiles), block(256);
-  const int cf = g->oscatter ? -1 : g->flags;
-#define NT_CASE(TY, F) case F: hipLaunchKernelGGL((gemm_nt_kernel<TY, F>), grid, block, 0, (hipStream_t)st, *g); break
-#define NT_SWITCH(TY)                                                                                   \
-  switch (cf) {                                                                                         \
-    NT_CASE(TY, 0); NT_CASE(TY, SODT_EPI_BIAS); NT_CASE(TY, SODT_EPI_RESID);                            \
-    NT_CASE(TY, (SODT_EPI_BIAS | SODT_EPI_RESID)); NT_CASE(TY, (SODT_EPI_BIAS | SODT_EPI_GELU_DUAL));   \
-    NT_CASE(TY, SODT_EPI_DGELU);                                                                        \
-    default: hipLaunchKernelGGL((gemm_nt_kernel<TY, -1>), grid, block, 0, (hipStream_t)st, *g); break;  \
-  }
-  if (dtype == SODT_BF16) { NT_SWITCH(bf16) }
-  else if (dtype == SODT_F32) { NT_SWITCH(float) }
-  else return SODT_EINVAL;
-#undef NT_SWITCH
-#undef NT_CASE
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  const NtRoute r = nt_route(*g, dtype, g_variant);
+  return dtype == SODT_BF16 ? launch_nt<bf16>(g, r, (hipStream_t)st) : launch_nt<float>(g, r, (hipStream_t)st);
 }
 
-extern "C" int sodt_gemm_set_variant(int force_tiled) {
-  g_force_tiled = force_tiled == 1;
-  g_variant = force_tiled;
+extern "C" int sodt_gemm_set_variant(int variant) {
+  g_variant = variant;
   return SODT_OK;
 }
 
 extern "C" int sodt_gemm_tn(const sodt_gemm_tn_args* g, int dtype, sodt_stream_t st) {
   if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0 || g->splits < 1 || !g->dW || !g->dY) return SODT_EINVAL;
+  if (dtype != SODT_BF16 && dtype != SODT_F32) return SODT_EINVAL;
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!aspec_ok(g->x, g->K, kpl)) return SODT_EINVAL;
   if ((g->ldy % kpl) || g->ldy < (g->N + kpl - 1) / kpl * kpl || (((uintptr_t)g->dY) & 15)) return SODT_EINVAL;
   if (g->kperm_t > 1 && (g->kperm_c <= 0 || g->kperm_c * g->kperm_t != g->K)) return SODT_EINVAL;
-  if (dtype == SODT_BF16 && g_variant == 0 && (g->N % 8) == 0 && (g->K % 8) == 0 && g->M >= 1024)
-    return sodt_tn3_launch(g, (hipStream_t)st);
-  if (!g_force_tiled && (g->N <= 192 || g->K <= 192)) {   // short side <= 192: the 256 x 192 tile reads each operand (almost) once
-    if (dtype == SODT_BF16) return launch_tn2<bf16>(g, (hipStream_t)st);
-    if (dtype == SODT_F32) return launch_tn2<float>(g, (hipStream_t)st);
-    return SODT_EINVAL;
+  const hipStream_t s_ = (hipStream_t)st;
+  const TnRoute r = tn_route(*g, dtype, g_variant);
+  switch (r.kind) {
+    case TN_PIPE: return sodt_tn3_launch(g, r, s_);
+    case TN_256x192: return dtype == SODT_BF16 ? launch_tn2<bf16>(g, s_) : launch_tn2<float>(g, s_);
+    case TN_TILED: break;
   }
   const int tiles = ((g->N + 127) / 128) * ((g->K + 127) / 128);
-  dim3 grid(tiles * g->splits), block(256);
-  if (dtype == SODT_BF16) {
-    hipLaunchKernelGGL(gemm_tn_kernel<bf16>, grid, block, 0, (hipStream_t)st, *g);
-  } else if (dtype == SODT_F32) {
-    hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, block, 0, (hipStream_t)st, *g);
-  } else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  const dim3 grid(tiles * g->splits), block(256);
+  return dtype == SODT_BF16 ? sodt_launch<gemm_tn_kernel<bf16>>(grid, block, 0, s_, *g)
+                            : sodt_launch<gemm_tn_kernel<float>>(grid, block, 0, s_, *g);
 }

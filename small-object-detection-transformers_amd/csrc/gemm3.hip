@@ -18,6 +18,8 @@
 // Roofline: MFMA-bound shapes (AI = 2NK/(2(K_in + N)) >= 300 flop/B for K >= 768); LDS traffic per K-step
 // 160 KB reads + 56 KB DMA writes per CU against 1536 MFMA cycles per SIMD.
 #include "gemm_epi.h"
+#include "launch.h"
+#include "routes.h"
 
 // scheduling experiments (tools/exp/ab_gemm3.sh): SODT_EXP_PRIO 1 = s_setprio(1) around every MFMA cluster (keeps hipcc from
 // moving MFMAs across the raw barriers: cdna_hip_programming.md T5); 2 = static priority for the younger half of the workgroup
@@ -38,19 +40,17 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
-constexpr int T3_BM = 256, T3_BN = 192, T3_BK = 64;
 constexpr int T3_AST = T3_BM * 128;                 // 32 KiB per A stage
 constexpr int T3_BST = T3_BN * 128;                 // 24 KiB per W stage
 constexpr int T3_BOFF = 3 * T3_AST;                 // W ring after the A ring
 constexpr int T3_SEGOFF = T3_BOFF + 2 * T3_BST;     // segment table (48 B per entry)
-constexpr int T3_BIASOFF = T3_SEGOFF + 448;         // f32 bias[N], N <= 3072 (read with inline-asm LDS loads in the epilogue:
-constexpr int T3_MAXBIAS = 3072;                    //  an ordinary global load there would drain the DMA queue every tile)
+constexpr int T3_BIASOFF = T3_SEGOFF + 448;         // f32 bias[N], N <= T3_MAXBIAS (read with inline-asm LDS loads in the epilogue:
+//                                                      an ordinary global load there would drain the DMA queue every tile)
 constexpr int T3_LDS = T3_BIASOFF + T3_MAXBIAS * 4;
 
 // DMA source of rows outside the image / beyond M.  8 KiB: such a row's source pointer advances by one K-step (128 B) per stage like
 // every other row's, up to the end of its K-segment (klen <= T3_MAXKLEN elements)
 __device__ uint4 g_zero16[512];
-constexpr int T3_MAXKLEN = (8192 - 256) / 2;
 
 __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(lds_void*)p; }
 
@@ -486,18 +486,9 @@ __global__ __launch_bounds__(512) void gemm_nt3_kernel(const sodt_gemm_args g) {
 
 template <int CF, bool OSC = false, int NV = 3>
 int launch_nt3(const sodt_gemm_args* g, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_nt3_kernel<CF, OSC, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, T3_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
   const long ntiles = (long)((g->M + T3_BM - 1) / T3_BM) * ((g->N + T3_BN - 1) / T3_BN);
   const int grid = (int)(ntiles < 256 ? ntiles : 256);
-  hipLaunchKernelGGL((gemm_nt3_kernel<CF, OSC, NV>), dim3(grid), dim3(512), T3_LDS, st, *g);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<gemm_nt3_kernel<CF, OSC, NV>>(dim3(grid), dim3(512), T3_LDS, st, *g);
 }
 
 
@@ -837,67 +828,29 @@ __global__ __launch_bounds__(256) void tn3_reduce_kernel(const float* __restrict
 
 template <bool SWAP, bool SPATIAL>
 int launch_tn3(const sodt_gemm_tn_args* g, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)gemm_tn3_kernel<SWAP, SPATIAL>, hipFuncAttributeMaxDynamicSharedMemorySize, N5_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
   const int Pdim = SWAP ? g->K : g->N, Qdim = SWAP ? g->N : g->K;
   const long tiles = (long)((Pdim + 255) / 256) * ((Qdim + 191) / 192);
   sodt_gemm_tn_args a = *g;
   const bool use_partial = a.partial && a.splits > 1 && (long)a.splits * a.N * a.K <= a.partial_floats &&
                            ((uintptr_t)a.partial & 15) == 0 && (a.lddw % 4) == 0 && ((uintptr_t)a.dW & 15) == 0;
   if (!use_partial) a.partial = nullptr;
-  hipLaunchKernelGGL((gemm_tn3_kernel<SWAP, SPATIAL>), dim3((unsigned)(tiles * a.splits)), dim3(512), N5_LDS, st, a);
-  if (use_partial) {
-    // slices past the end of M launch no work and write no partial tile: the reduction reads only the live ones
-    const long rows_per = ((((long)a.M + a.splits - 1) / a.splits) + N5_ROWS - 1) / N5_ROWS * N5_ROWS;
-    const int live = (int)(((long)a.M + rows_per - 1) / rows_per);
-    const long nk4 = (long)a.N * a.K / 4;
-    const int blocks = (int)((nk4 + 63) / 64);
-    hipLaunchKernelGGL(tn3_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)a.partial, a.dW, a.N, a.K, a.lddw,
-                       live, a.kperm_c, a.kperm_t);
-  }
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  const int rc = sodt_launch<gemm_tn3_kernel<SWAP, SPATIAL>>(dim3((unsigned)(tiles * a.splits)), dim3(512), N5_LDS, st, a);
+  if (rc || !use_partial) return rc;
+  // slices past the end of M launch no work and write no partial tile: the reduction reads only the live ones
+  const long rows_per = ((((long)a.M + a.splits - 1) / a.splits) + N5_ROWS - 1) / N5_ROWS * N5_ROWS;
+  const int live = (int)(((long)a.M + rows_per - 1) / rows_per);
+  const long nk4 = (long)a.N * a.K / 4;
+  const int blocks = (int)((nk4 + 63) / 64);
+  return sodt_launch<tn3_reduce_kernel>(dim3(blocks), dim3(256), 0, st, (const float*)a.partial, a.dW, a.N, a.K, a.lddw,
+                                        live, a.kperm_c, a.kperm_t);
 }
 
 }  // namespace
 
-// eligibility of the pipelined kernel (bf16 only); the caller has validated pointers / alignment
-bool sodt_nt3_eligible(const sodt_gemm_args* g) {
-  switch (g->flags) {
-    case 0: case SODT_EPI_BIAS: case SODT_EPI_RESID: case SODT_EPI_BIAS | SODT_EPI_RESID:
-    case SODT_EPI_BIAS | SODT_EPI_GELU_DUAL: case SODT_EPI_DGELU: case SODT_EPI_BIAS | SODT_EPI_GELU: break;
-    case SODT_EPI_RELU: case SODT_EPI_BIAS | SODT_EPI_RELU: case SODT_EPI_DRELU: break;      // the SR branch's convolutions (sr.py)
-    case SODT_EPI_STATS:                           // the head's BatchNorm convolutions, thin outputs only (one column tile, NV = 2)
-      if (g->N > 64 || !g->stats || g->oscatter) return false;
-      break;
-    case SODT_EPI_BIAS | SODT_EPI_DGELU_RC:
-      if (g->K % (2 * T3_BK)) return false;        // both halves whole K-steps
-      break;
-    default: return false;
-  }
-  if (g->rmod > 0 || (g->oscatter && (g->flags != 0 || !g->a.spatial))) return false;
-  // N: whole 192-column tiles, or (K >= 512) any multiple of 8 with the last tile partial - a narrow output (the 64-channel 3x3
-  // convolutions of the SR branch, the 256-wide ones of its tail) is priced by the A stream, which this kernel moves by LDS-DMA
-  // three stages ahead; the idle accumulator columns cost matrix cycles that are not the bound there
-  const int kmin_partial = g->flags == SODT_EPI_STATS ? 192 : 512;     // (statistics: the alternative is the 128 x 128 K-loop kernel)
-  if (g->N % 8 || (g->N % T3_BN && (g->K < kmin_partial || g->K > T3_MAXKLEN)) || g->K % T3_BK || g->K < 192 || g->M < T3_BM) return false;
-  if ((g->flags & SODT_EPI_RESID) && (g->ldr % 8)) return false;
-  if ((g->flags & (SODT_EPI_DGELU | SODT_EPI_DRELU)) && (g->ldaux % 8)) return false;
-  if ((g->flags & SODT_EPI_BIAS) && g->N > T3_MAXBIAS) return false;
-  if ((g->ldw % 8) || (g->ldc % 8)) return false;
-  for (int i = 0; i < g->a.nseg; ++i)
-    if (g->a.s[i].klen % T3_BK || g->a.s[i].klen > T3_MAXKLEN) return false;
-  return true;
-}
-
-int sodt_nt3_launch(const sodt_gemm_args* g, hipStream_t st) {
-  if (g->N <= 64 && !g->oscatter) {          // thin output (the 64-channel 3x3 convolutions of the SR branch and the head): NV = 2
-    switch (g->flags) {
+// the pipelined NT kernel under nt_route()'s NT_PIPE
+int sodt_nt3_launch(const sodt_gemm_args* g, const NtRoute& r, hipStream_t st) {
+  if (r.thin) {
+    switch (r.cf) {
       case 0: return launch_nt3<0, false, 2>(g, st);
       case SODT_EPI_BIAS: return launch_nt3<SODT_EPI_BIAS, false, 2>(g, st);
       case SODT_EPI_BIAS | SODT_EPI_RESID: return launch_nt3<SODT_EPI_BIAS | SODT_EPI_RESID, false, 2>(g, st);
@@ -905,11 +858,11 @@ int sodt_nt3_launch(const sodt_gemm_args* g, hipStream_t st) {
       case SODT_EPI_BIAS | SODT_EPI_RELU: return launch_nt3<SODT_EPI_BIAS | SODT_EPI_RELU, false, 2>(g, st);
       case SODT_EPI_DRELU: return launch_nt3<SODT_EPI_DRELU, false, 2>(g, st);
       case SODT_EPI_STATS: return launch_nt3<SODT_EPI_STATS, false, 2>(g, st);
-      default: break;
+      default: return SODT_EINVAL;
     }
   }
-  switch (g->flags) {
-    case 0: return g->oscatter ? launch_nt3<0, true>(g, st) : launch_nt3<0>(g, st);
+  switch (r.cf) {
+    case 0: return r.scatter ? launch_nt3<0, true>(g, st) : launch_nt3<0>(g, st);
     case SODT_EPI_BIAS: return launch_nt3<SODT_EPI_BIAS>(g, st);
     case SODT_EPI_RESID: return launch_nt3<SODT_EPI_RESID>(g, st);
     case SODT_EPI_BIAS | SODT_EPI_RESID: return launch_nt3<SODT_EPI_BIAS | SODT_EPI_RESID>(g, st);
@@ -924,15 +877,8 @@ int sodt_nt3_launch(const sodt_gemm_args* g, hipStream_t st) {
   }
 }
 
-// pipelined TN: K on the 256-wide side when that pads less (ties keep N there); mirrored by ops.tn_splits
-bool sodt_tn3_swap(int N, int K) {
-  const long a = (long)((N + 255) / 256) * 256 * ((K + 191) / 192) * 192;
-  const long b = (long)((K + 255) / 256) * 256 * ((N + 191) / 192) * 192;
-  return b < a;
-}
-
-int sodt_tn3_launch(const sodt_gemm_tn_args* g, hipStream_t st) {
-  const bool sw = sodt_tn3_swap(g->N, g->K);
-  if (g->x.spatial) return sw ? launch_tn3<true, true>(g, st) : launch_tn3<false, true>(g, st);
-  return sw ? launch_tn3<true, false>(g, st) : launch_tn3<false, false>(g, st);
+// the pipelined TN kernel under tn_route()'s TN_PIPE
+int sodt_tn3_launch(const sodt_gemm_tn_args* g, const TnRoute& r, hipStream_t st) {
+  if (r.spatial) return r.swap ? launch_tn3<true, true>(g, st) : launch_tn3<false, true>(g, st);
+  return r.swap ? launch_tn3<true, false>(g, st) : launch_tn3<false, false>(g, st);
 }

@@ -4,6 +4,7 @@
 //   Concat slot copies (models/model.yaml:66-72), Detect's permutes and eval decode
 //   (model.py:55-64), parameter preparation.  All token-major, 16-byte accesses.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -380,16 +381,14 @@ inline unsigned nblocks(long work, int cap = 4096) {
 extern "C" int sodt_bn_finalize(const double* stats, float* mean_rstd, float* running_mean, float* running_var,
                                 long count, int C, float eps, float momentum, sodt_stream_t st) {
   if (!mean_rstd || C <= 0 || (!stats && (!running_mean || !running_var))) return SODT_EINVAL;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)st, stats, mean_rstd,
+  return sodt_launch<bn_finalize_kernel>(dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)st, stats, mean_rstd,
                      running_mean, running_var, count, C, eps, momentum);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_bn_affine(const float* mean_rstd, const float* gamma, const float* beta, float* scale, float* shift,
                               int C, sodt_stream_t st) {
   if (!mean_rstd || !gamma || !beta || !scale || !shift || C <= 0) return SODT_EINVAL;
-  hipLaunchKernelGGL(bn_affine_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)st, mean_rstd, gamma, beta, scale, shift, C);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<bn_affine_kernel>(dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)st, mean_rstd, gamma, beta, scale, shift, C);
 }
 
 extern "C" int sodt_bn_silu_fwd(const void* z, const float* mean_rstd, const float* gamma, const float* beta,
@@ -397,10 +396,9 @@ extern "C" int sodt_bn_silu_fwd(const void* z, const float* mean_rstd, const flo
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!z || !y || M <= 0 || C <= 0 || (C % kpl) || (ldy % kpl)) return SODT_EINVAL;
   const unsigned gr = nblocks(M * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(bn_silu_fwd_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)z, mean_rstd, gamma, beta, (bf16*)y, ldy, M, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(bn_silu_fwd_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)z, mean_rstd, gamma, beta, (float*)y, ldy, M, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_fwd_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)z, mean_rstd, gamma, beta, (bf16*)y, ldy, M, C);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_fwd_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)z, mean_rstd, gamma, beta, (float*)y, ldy, M, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_bn_silu_bwd_reduce(const void* dy, int lddy, const void* z, const float* mean_rstd,
@@ -410,10 +408,9 @@ extern "C" int sodt_bn_silu_bwd_reduce(const void* dy, int lddy, const void* z, 
   if (!dy || !z || !red || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
   const int rpp = 256 / (C / kpl);
   long gr = (M + rpp - 1) / rpp; if (gr > 1024) gr = 1024;
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel<bf16>, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, M, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel<float>, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, M, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_reduce_kernel<bf16>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, M, C);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_reduce_kernel<float>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, M, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_col_stats(const void* z, int ldz, double* stats, long M, int C, int dtype, sodt_stream_t st) {
@@ -421,10 +418,9 @@ extern "C" int sodt_col_stats(const void* z, int ldz, double* stats, long M, int
   if (!z || !stats || M <= 0 || C <= 0 || (C % kpl) || (ldz % kpl) || C / kpl > 256 || (((uintptr_t)z) & 15)) return SODT_EINVAL;
   const int rpp = 256 / (C / kpl);
   long gr = (M + 4L * rpp - 1) / (4L * rpp); if (gr > 1024) gr = 1024;
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(col_stats_kernel<bf16>, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const bf16*)z, ldz, stats, M, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(col_stats_kernel<float>, dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const float*)z, ldz, stats, M, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<col_stats_kernel<bf16>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const bf16*)z, ldz, stats, M, C);
+  if (dtype == SODT_F32) return sodt_launch<col_stats_kernel<float>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const float*)z, ldz, stats, M, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, const float* mean_rstd,
@@ -433,10 +429,9 @@ extern "C" int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, c
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!dy || !z || !red || !dz || !dgamma || !dbeta || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl)) return SODT_EINVAL;
   const unsigned gr = nblocks(M * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(bn_silu_bwd_apply_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(bn_silu_bwd_apply_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_copy_rows(const void* src, int lds_, void* dst, int ldd, int B, int Ho, int Wo, int shr, int C,
@@ -445,10 +440,9 @@ extern "C" int sodt_copy_rows(const void* src, int lds_, void* dst, int ldd, int
   if (!src || !dst || B <= 0 || Ho <= 0 || Wo <= 0 || shr < 0 || C <= 0 || (C % kpl) || (lds_ % kpl) || (ldd % kpl)) return SODT_EINVAL;
   if ((Ho & ((1 << shr) - 1)) || (Wo & ((1 << shr) - 1))) return SODT_EINVAL;
   const unsigned gr = nblocks((long)B * Ho * Wo * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(copy_rows_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)src, lds_, (bf16*)dst, ldd, B, Ho, Wo, shr, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(copy_rows_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, lds_, (float*)dst, ldd, B, Ho, Wo, shr, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<copy_rows_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)src, lds_, (bf16*)dst, ldd, B, Ho, Wo, shr, C);
+  if (dtype == SODT_F32) return sodt_launch<copy_rows_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, lds_, (float*)dst, ldd, B, Ho, Wo, shr, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_gather_sum_rows(const void* d, int ldd, void* dsrc, int lds_, int B, int Hs, int Ws, int shr, int C,
@@ -456,67 +450,60 @@ extern "C" int sodt_gather_sum_rows(const void* d, int ldd, void* dsrc, int lds_
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!d || !dsrc || B <= 0 || Hs <= 0 || Ws <= 0 || shr < 0 || C <= 0 || (C % kpl) || (lds_ % kpl) || (ldd % kpl)) return SODT_EINVAL;
   const unsigned gr = nblocks((long)B * Hs * Ws * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(gather_sum_rows_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)d, ldd, (bf16*)dsrc, lds_, B, Hs, Ws, shr, C, accumulate);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(gather_sum_rows_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)d, ldd, (float*)dsrc, lds_, B, Hs, Ws, shr, C, accumulate);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<gather_sum_rows_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)d, ldd, (bf16*)dsrc, lds_, B, Hs, Ws, shr, C, accumulate);
+  if (dtype == SODT_F32) return sodt_launch<gather_sum_rows_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)d, ldd, (float*)dsrc, lds_, B, Hs, Ws, shr, C, accumulate);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_detect_unpermute(const float* dpred, void* dz, int ldz, int B, int HW, int na, int no,
                                      int dtype, sodt_stream_t st) {
   if (!dpred || !dz || B <= 0 || HW <= 0 || na * no > ldz) return SODT_EINVAL;
   const unsigned gr = nblocks((long)B * HW * ldz);
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(detect_unpermute_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, dpred, (bf16*)dz, ldz, B, HW, na, no);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(detect_unpermute_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, dpred, (float*)dz, ldz, B, HW, na, no);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<detect_unpermute_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, dpred, (bf16*)dz, ldz, B, HW, na, no);
+  if (dtype == SODT_F32) return sodt_launch<detect_unpermute_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, dpred, (float*)dz, ldz, B, HW, na, no);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_detect_decode(const float* raw, const float* anchor_grid, float* z, int B, int na, int ny, int nx,
                                   int no, float stride, sodt_stream_t st) {
   if (!raw || !anchor_grid || !z || B <= 0 || na <= 0 || ny <= 0 || nx <= 0 || no < 5) return SODT_EINVAL;
-  hipLaunchKernelGGL(detect_decode_kernel, dim3(nblocks((long)B * na * ny * nx * no)), dim3(256), 0, (hipStream_t)st,
+  return sodt_launch<detect_decode_kernel>(dim3(nblocks((long)B * na * ny * nx * no)), dim3(256), 0, (hipStream_t)st,
                      raw, anchor_grid, z, B, na, ny, nx, no, stride);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_prep_weights(const sodt_prep_desc* table_dev, int n, int max_elems, int dtype, sodt_stream_t st) {
   if (!table_dev || n <= 0 || max_elems <= 0) return SODT_EINVAL;
   unsigned bx = nblocks(max_elems / 4, 512);   // the largest weights (768 x 3072) are 2304 transpose tiles: 64 blocks walked 36 tiles each, one latency chain per tile
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(prep_kernel<bf16>, dim3(bx, n), dim3(256), 0, (hipStream_t)st, table_dev, n);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(prep_kernel<float>, dim3(bx, n), dim3(256), 0, (hipStream_t)st, table_dev, n);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<prep_kernel<bf16>>(dim3(bx, n), dim3(256), 0, (hipStream_t)st, table_dev, n);
+  if (dtype == SODT_F32) return sodt_launch<prep_kernel<float>>(dim3(bx, n), dim3(256), 0, (hipStream_t)st, table_dev, n);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_transpose_f32(const float* src, float* dst, int rows, int cols, int accumulate, sodt_stream_t st) {
   if (!src || !dst || rows <= 0 || cols <= 0) return SODT_EINVAL;
-  hipLaunchKernelGGL(transpose_f32_kernel, dim3(nblocks((long)rows * cols)), dim3(256), 0, (hipStream_t)st, src, dst, rows, cols, accumulate);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<transpose_f32_kernel>(dim3(nblocks((long)rows * cols)), dim3(256), 0, (hipStream_t)st, src, dst, rows, cols, accumulate);
 }
 
 extern "C" int sodt_cast(const void* src, void* dst, long n, int src_dtype, int dst_dtype, sodt_stream_t st) {
   if (!src || !dst || n <= 0) return SODT_EINVAL;
   const unsigned gr = nblocks(n);
-  if (src_dtype == SODT_F32 && dst_dtype == SODT_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16>), dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, (bf16*)dst, n);
-  else if (src_dtype == SODT_BF16 && dst_dtype == SODT_F32) hipLaunchKernelGGL((cast_kernel<bf16, float>), dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)src, (float*)dst, n);
-  else if (src_dtype == SODT_F32 && dst_dtype == SODT_F32) hipLaunchKernelGGL((cast_kernel<float, float>), dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, (float*)dst, n);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (src_dtype == SODT_F32 && dst_dtype == SODT_BF16) return sodt_launch<cast_kernel<float, bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, (bf16*)dst, n);
+  if (src_dtype == SODT_BF16 && dst_dtype == SODT_F32) return sodt_launch<cast_kernel<bf16, float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)src, (float*)dst, n);
+  if (src_dtype == SODT_F32 && dst_dtype == SODT_F32) return sodt_launch<cast_kernel<float, float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)src, (float*)dst, n);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_batch_sum(const void* d, float* out, int B, long RC, int dtype, sodt_stream_t st) {
   if (!d || !out || B <= 0 || RC <= 0) return SODT_EINVAL;
   const unsigned gr = nblocks(RC / 4);
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(batch_sum_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)d, out, B, RC);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(batch_sum_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)d, out, B, RC);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<batch_sum_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)d, out, B, RC);
+  if (dtype == SODT_F32) return sodt_launch<batch_sum_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)d, out, B, RC);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_memset_zero(void* p, long bytes, sodt_stream_t st) {
   if (!p || bytes <= 0) return SODT_EINVAL;
-  return hipMemsetAsync(p, 0, (size_t)bytes, (hipStream_t)st) == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return hipMemsetAsync(p, 0, (size_t)bytes, (hipStream_t)st) == hipSuccess ? SODT_OK : SODT_ELAUNCH;
 }
 
 extern "C" const char* sodt_version(void) { return "sodt_hip 0.1 (gfx950)"; }

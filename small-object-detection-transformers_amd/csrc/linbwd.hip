@@ -21,6 +21,7 @@
 //     live slices in a fixed order (run-to-run deterministic).  Without a scratch that fits: f32 atomics.
 // Cost: 144 + 144 MFMAs per stage and CU against 36 KiB of HBM traffic - memory-priced.
 #include "gemm_epi.h"
+#include "launch.h"
 
 namespace {
 
@@ -361,16 +362,7 @@ __global__ __launch_bounds__(256) void linbwd_reduce_kernel(const float* __restr
 
 template <bool DG>
 int launch_linbwd(const sodt_linbwd_args* g, float* partial, float* bpartial, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)linbwd_sq_kernel<DG>, hipFuncAttributeMaxDynamicSharedMemorySize, LB_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((linbwd_sq_kernel<DG>), dim3((unsigned)g->splits), dim3(512), LB_LDS, st, *g, partial, bpartial);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<linbwd_sq_kernel<DG>>(dim3((unsigned)g->splits), dim3(512), LB_LDS, st, *g, partial, bpartial);
 }
 
 }  // namespace
@@ -394,14 +386,10 @@ extern "C" int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_str
   float* bpartial = (use_partial && g->dbias && tile_floats + (long)g->splits * LB_C <= g->partial_floats) ? g->partial + tile_floats : nullptr;
   const int rc = (g->flags & SODT_EPI_DGELU) ? launch_linbwd<true>(g, partial, bpartial, (hipStream_t)st)
                                              : launch_linbwd<false>(g, partial, bpartial, (hipStream_t)st);
-  if (rc != SODT_OK) return rc;
-  if (use_partial) {
-    const long rows_per = ((((long)g->M + g->splits - 1) / g->splits) + LB_ROWS - 1) / LB_ROWS * LB_ROWS;
-    const int live = (int)(((long)g->M + rows_per - 1) / rows_per);
-    const int wblocks = LB_C * LB_C / 4 / 64;
-    hipLaunchKernelGGL(linbwd_reduce_kernel, dim3(wblocks + (bpartial ? 1 : 0)), dim3(256), 0, (hipStream_t)st, (const float*)partial,
-                       g->dW, g->lddw, live, (const float*)bpartial, g->dbias, wblocks);
-    if (hipGetLastError() != hipSuccess) return SODT_EINVAL;
-  }
-  return SODT_OK;
+  if (rc || !use_partial) return rc;
+  const long rows_per = ((((long)g->M + g->splits - 1) / g->splits) + LB_ROWS - 1) / LB_ROWS * LB_ROWS;
+  const int live = (int)(((long)g->M + rows_per - 1) / rows_per);
+  const int wblocks = LB_C * LB_C / 4 / 64;
+  return sodt_launch<linbwd_reduce_kernel>(dim3(wblocks + (bpartial ? 1 : 0)), dim3(256), 0, (hipStream_t)st, (const float*)partial,
+                                           g->dW, g->lddw, live, (const float*)bpartial, g->dbias, wblocks);
 }

@@ -28,6 +28,7 @@
 // FOCAL = false instantiations, which are the kernels as they were before focal loss existed.
 // Latency-bound (a few hundred candidates), except obj_dense which streams pred / dpred once: 2 x B*na*ny*nx*no*4 bytes.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -243,20 +244,21 @@ int yolo_loss(const float* pred, const float* targets, int nt, const float* anch
   a.h_box = h_box; a.h_cls = h_cls; a.cls_pw = cls_pw; a.h_obj = h_obj; a.obj_pw = obj_pw; a.anchor_t = anchor_t; a.gr = gr;
   a.fl_gamma = fl_gamma;
   const bool focal = fl_gamma > 0.f;
-  if (hipMemsetAsync(w, 0xff, win, st) != hipSuccess) return SODT_EINVAL;          // winner = -1
-  if (hipMemsetAsync(w + win, 0, 256, st) != hipSuccess) return SODT_EINVAL;       // sums = 0
+  if (hipMemsetAsync(w, 0xff, win, st) != hipSuccess) return SODT_ELAUNCH;          // winner = -1
+  if (hipMemsetAsync(w + win, 0, 256, st) != hipSuccess) return SODT_ELAUNCH;       // sums = 0
   const int ncand = 5 * na * nt;
   if (ncand > 0) {
-    if (focal) hipLaunchKernelGGL(loss_candidates_kernel<true>, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL(loss_candidates_kernel<false>, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
+    if (int err = focal ? sodt_launch<loss_candidates_kernel<true>>(dim3((ncand + 127) / 128), dim3(128), 0, st, a)
+                        : sodt_launch<loss_candidates_kernel<false>>(dim3((ncand + 127) / 128), dim3(128), 0, st, a)) return err;
   }
   long nb = (ncells + 255) / 256;
   if (nb > 2048) nb = 2048;
-  if (focal) hipLaunchKernelGGL(loss_obj_dense_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, a, ncells);
-  else hipLaunchKernelGGL(loss_obj_dense_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, a, ncells);
-  if (ncand > 0) hipLaunchKernelGGL(loss_scatter_kernel, dim3((ncand + 127) / 128), dim3(128), 0, st, a);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, st, a, ncells);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (int err = focal ? sodt_launch<loss_obj_dense_kernel<true>>(dim3((unsigned)nb), dim3(256), 0, st, a, ncells)
+                      : sodt_launch<loss_obj_dense_kernel<false>>(dim3((unsigned)nb), dim3(256), 0, st, a, ncells)) return err;
+  if (ncand > 0) {
+    if (int err = sodt_launch<loss_scatter_kernel>(dim3((ncand + 127) / 128), dim3(128), 0, st, a)) return err;
+  }
+  return sodt_launch<loss_finalize_kernel>(dim3(1), dim3(1), 0, st, a, ncells);
 }
 
 }  // namespace

@@ -40,6 +40,7 @@
 #include <rocprim/block/block_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -166,7 +167,7 @@ int match_layout_of(int B, long n_det, long nt, match_layout& L) {
   size_t tb = 0;
   if (nt > 0 && rocprim::radix_sort_pairs<rocprim::default_config, const uint32_t*, uint32_t*, const uint32_t*, uint32_t*>(
                     nullptr, tb, nullptr, nullptr, nullptr, nullptr, (size_t)nt, 0, bits_for((unsigned long)B)) != hipSuccess)
-    return SODT_EINVAL;
+    return SODT_ELAUNCH;
   size_t o = 0;
   L.keys_in = o; o += align256((size_t)nt * 4);
   L.keys_out = o; o += align256((size_t)nt * 4);
@@ -496,7 +497,7 @@ int ap_layout_of(long n, long nt, int nc, ap_layout& L) {
   size_t tb = 0;
   if (n > 0 && rocprim::radix_sort_pairs<rocprim::default_config, const uint64_t*, uint64_t*, const uint32_t*, uint32_t*>(
                    nullptr, tb, nullptr, nullptr, nullptr, nullptr, (size_t)n, 0, 32 + bits_for((unsigned long)nc)) != hipSuccess)
-    return SODT_EINVAL;
+    return SODT_ELAUNCH;
   size_t o = 0;
   L.keys_in = o; o += align256((size_t)n * 8);
   L.keys_out = o; o += align256((size_t)n * 8);
@@ -645,7 +646,7 @@ int confusion_layout_of(int B, long n_det, long nt, confusion_layout& L) {
   size_t tb = 0;
   if (nt > 0 && rocprim::radix_sort_pairs<rocprim::default_config, const uint32_t*, uint32_t*, const uint32_t*, uint32_t*>(
                     nullptr, tb, nullptr, nullptr, nullptr, nullptr, (size_t)nt, 0, bits_for((unsigned long)B)) != hipSuccess)
-    return SODT_EINVAL;
+    return SODT_ELAUNCH;
   size_t o = 0;
   L.keys_in = o; o += align256((size_t)nt * 4);
   L.keys_out = o; o += align256((size_t)nt * 4);
@@ -686,17 +687,16 @@ extern "C" int sodt_eval_match(const float* det, const int* det_off, int B, long
   int* toff = (int*)(base + L.toff);
   const int ntt = (int)nt;
   if (ntt > 0) {
-    match_keys_kernel<<<(ntt + 255) / 256, 256, 0, stream>>>(targets, ntt, B, keys_in, rows_in);
+    if (int err = sodt_launch<match_keys_kernel>(dim3((ntt + 255) / 256), dim3(256), 0, stream, targets, ntt, B, keys_in, rows_in)) return err;
     size_t tb = L.sort_tmp_bytes;
     if (rocprim::radix_sort_pairs(base + L.sort_tmp, tb, (const uint32_t*)keys_in, keys_out, (const uint32_t*)rows_in,
                                   rows_out, (size_t)ntt, 0, bits_for((unsigned long)B), stream) != hipSuccess)
-      return SODT_EINVAL;
+      return SODT_ELAUNCH;
   }
-  match_offsets_kernel<<<(B + 1 + 255) / 256, 256, 0, stream>>>(keys_out, ntt, B, toff);
-  match_image_kernel<<<B, TPB, 0, stream>>>(det, det_off, (int)n_det, B, targets, ntt, rows_out, toff, geom, thr,
+  if (int err = sodt_launch<match_offsets_kernel>(dim3((B + 1 + 255) / 256), dim3(256), 0, stream, keys_out, ntt, B, toff)) return err;
+  return sodt_launch<match_image_kernel>(B, TPB, 0, stream, det, det_off, (int)n_det, B, targets, ntt, rows_out, toff, geom, thr,
                                             (float4*)(base + L.tbox), (float*)(base + L.tcls), (int*)(base + L.claim),
                                             (int*)(base + L.best_t), (float*)(base + L.best_iou), correct, tcls_out);
-  return SODT_OK;
 }
 
 extern "C" int sodt_ap_per_class_workspace_bytes(long n, long nt, int nc, size_t* bytes) {
@@ -729,23 +729,22 @@ extern "C" int sodt_ap_per_class(const unsigned char* tp, const float* conf, con
   double* pc = (double*)(base + L.pcurve);
   double* rc = (double*)(base + L.rcurve);
   // n_l, n_p and seg are adjacent: one clear covers the counters
-  if (hipMemsetAsync(n_l, 0, L.seg - L.n_l, stream) != hipSuccess) return SODT_EINVAL;
-  if (hipMemsetAsync(info, 0, 4 * sizeof(int), stream) != hipSuccess) return SODT_EINVAL;
+  if (hipMemsetAsync(n_l, 0, L.seg - L.n_l, stream) != hipSuccess) return SODT_ELAUNCH;
+  if (hipMemsetAsync(info, 0, 4 * sizeof(int), stream) != hipSuccess) return SODT_ELAUNCH;
   const long m = n > nt ? n : nt;
   if (m > 0)
-    ap_hist_kernel<<<(int)((m + 255) / 256), 256, 0, stream>>>(tp, conf, pred_cls, (int)n, target_cls, (int)nt, nc,
-                                                              keys_in, rows_in, n_l, n_p, info);
+    if (int err = sodt_launch<ap_hist_kernel>(dim3((int)((m + 255) / 256)), dim3(256), 0, stream, tp, conf, pred_cls, (int)n, target_cls, (int)nt, nc,
+                                                              keys_in, rows_in, n_l, n_p, info)) return err;
   if (n > 0) {
     size_t tb = L.sort_tmp_bytes;
     if (rocprim::radix_sort_pairs(base + L.sort_tmp, tb, (const uint64_t*)keys_in, keys_out, (const uint32_t*)rows_in,
                                   rows_out, (size_t)n, 0, 32 + bits_for((unsigned long)nc), stream) != hipSuccess)
-      return SODT_EINVAL;
+      return SODT_ELAUNCH;
   }
-  ap_classes_kernel<<<1, TPB, 0, stream>>>(n_l, n_p, nc, seg, ci_of, classes, nt_count, info);
-  if (n > 0) ap_scan_kernel<<<nc, TPB, 0, stream>>>(tp, conf, rows_out, seg, n_l, tpc, env, conf_s);
-  ap_curves_kernel<<<nc, TPB, 0, stream>>>(seg, n_l, ci_of, tpc, env, conf_s, pc, rc, ap);
-  ap_finalize_kernel<<<1, 1024, 0, stream>>>(pc, rc, info, p, r, f1);
-  return SODT_OK;
+  if (int err = sodt_launch<ap_classes_kernel>(dim3(1), TPB, 0, stream, n_l, n_p, nc, seg, ci_of, classes, nt_count, info)) return err;
+  if (n > 0) { if (int err = sodt_launch<ap_scan_kernel>(nc, TPB, 0, stream, tp, conf, rows_out, seg, n_l, tpc, env, conf_s)) return err; }
+  if (int err = sodt_launch<ap_curves_kernel>(nc, TPB, 0, stream, seg, n_l, ci_of, tpc, env, conf_s, pc, rc, ap)) return err;
+  return sodt_launch<ap_finalize_kernel>(dim3(1), dim3(1024), 0, stream, pc, rc, info, p, r, f1);
 }
 
 extern "C" int sodt_confusion_update_workspace_bytes(int B, long n_det, long nt, size_t* bytes) {
@@ -770,15 +769,14 @@ extern "C" int sodt_confusion_update(const float* det, const int* det_off, int B
   int* toff = (int*)(base + L.toff);
   const int ntt = (int)nt;
   if (ntt > 0) {   // group the targets by image exactly as sodt_eval_match does: a stable sort keeps each image's row order
-    match_keys_kernel<<<(ntt + 255) / 256, 256, 0, stream>>>(targets, ntt, B, keys_in, rows_in);
+    if (int err = sodt_launch<match_keys_kernel>(dim3((ntt + 255) / 256), dim3(256), 0, stream, targets, ntt, B, keys_in, rows_in)) return err;
     size_t tb = L.sort_tmp_bytes;
     if (rocprim::radix_sort_pairs(base + L.sort_tmp, tb, (const uint32_t*)keys_in, keys_out, (const uint32_t*)rows_in,
                                   rows_out, (size_t)ntt, 0, bits_for((unsigned long)B), stream) != hipSuccess)
-      return SODT_EINVAL;
+      return SODT_ELAUNCH;
   }
-  match_offsets_kernel<<<(B + 1 + 255) / 256, 256, 0, stream>>>(keys_out, ntt, B, toff);
-  confusion_image_kernel<<<B, TPB, 0, stream>>>(det, det_off, (int)n_det, targets, rows_out, toff, geom, nc, conf, iou_thres,
+  if (int err = sodt_launch<match_offsets_kernel>(dim3((B + 1 + 255) / 256), dim3(256), 0, stream, keys_out, ntt, B, toff)) return err;
+  return sodt_launch<confusion_image_kernel>(B, TPB, 0, stream, det, det_off, (int)n_det, targets, rows_out, toff, geom, nc, conf, iou_thres,
                                                 (float4*)(base + L.tbox), (unsigned long long*)(base + L.dkey),
                                                 (unsigned long long*)(base + L.lkey), (unsigned long long*)matrix, info);
-  return SODT_OK;
 }

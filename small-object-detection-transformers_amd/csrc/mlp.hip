@@ -28,6 +28,7 @@
 // Roofline: 16 T C^2 flops over 3 T C 2 B (inference) = 309 GFLOP / 604 MB at stage 1 of B=8 @1024^2: MFMA-bound by AI (512 flop/B);
 // with the GELU(h) store (training) 1.41 GB: HBM-priced (0.28 ms at 5 TB/s against 0.12 ms of matrix time).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -403,18 +404,9 @@ __global__ __launch_bounds__(512) void mlp_fwd_kernel(const MlpArgs g) {
 }
 
 template <bool SAVE, bool RES> int launch_mlp(const MlpArgs& a, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)mlp_fwd_kernel<SAVE, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, ML_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
   const long ntiles = (a.M + ML_BM - 1) / ML_BM;
   const int grid = (int)(ntiles < 256 ? ntiles : 256);
-  hipLaunchKernelGGL((mlp_fwd_kernel<SAVE, RES>), dim3(grid), dim3(512), ML_LDS, st, a);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<mlp_fwd_kernel<SAVE, RES>>(dim3(grid), dim3(512), ML_LDS, st, a);
 }
 
 }  // namespace
@@ -455,6 +447,6 @@ extern "C" int sodt_mlp_fwd(const void* xn, const void* w1, const float* b1, con
 
 #ifdef ML_STAMPS
 extern "C" int sodt_debug_mlp_stamps(unsigned long long* host_256x8x8) {
-  return hipMemcpyFromSymbol(host_256x8x8, HIP_SYMBOL(g_mlp_stamps), sizeof(unsigned long long) * 256 * 8 * 8) == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return hipMemcpyFromSymbol(host_256x8x8, HIP_SYMBOL(g_mlp_stamps), sizeof(unsigned long long) * 256 * 8 * 8) == hipSuccess ? SODT_OK : SODT_ELAUNCH;
 }
 #endif

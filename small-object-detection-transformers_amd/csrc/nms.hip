@@ -20,6 +20,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -210,7 +211,7 @@ int layout(long n_total, ws_layout& L) {
   size_t tb = 0;
   if (n_total > 0 && rocprim::radix_sort_keys<rocprim::default_config, const uint64_t*, uint64_t*>(
           nullptr, tb, nullptr, nullptr, (size_t)n_total, 0, 64, 0) != hipSuccess)
-    return SODT_EINVAL;
+    return SODT_ELAUNCH;
   size_t o = 0;
   L.keys_sorted = o; o += align256((size_t)n_total * 8);
   L.sort_tmp = o; L.sort_tmp_bytes = tb; o += align256(tb);
@@ -231,10 +232,9 @@ extern "C" int sodt_nms_candidates(const float* z, int N, int nc, float conf_thr
                                    const unsigned char* class_allow, unsigned long long* keys, int cap, int* count,
                                    hipStream_t stream) {
   if (!z || !keys || !count || N <= 0 || nc <= 0 || cap <= 0 || (long)N * nc > 0x7fffffffL) return SODT_EINVAL;
-  if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) return SODT_EINVAL;
-  nms_candidates_kernel<<<(N + 255) / 256, 256, 0, stream>>>(z, N, nc, conf_thres, multi_label && nc > 1, class_allow,
+  if (hipMemsetAsync(count, 0, sizeof(int), stream) != hipSuccess) return SODT_ELAUNCH;
+  return sodt_launch<nms_candidates_kernel>(dim3((N + 255) / 256), dim3(256), 0, stream, z, N, nc, conf_thres, multi_label && nc > 1, class_allow,
                                                              (uint64_t*)keys, cap, count);
-  return SODT_OK;
 }
 
 extern "C" int sodt_nms_workspace_bytes(long n_total, size_t* bytes) {
@@ -254,7 +254,7 @@ extern "C" int sodt_nms_select(const float* z, int nc, const unsigned long long*
   uint64_t* ks = (uint64_t*)(base + L.keys_sorted);
   size_t tb = L.sort_tmp_bytes;
   if (rocprim::radix_sort_keys(base + L.sort_tmp, tb, (const uint64_t*)keys, ks, (size_t)n_total, 0, 64, stream) != hipSuccess)
-    return SODT_EINVAL;
+    return SODT_ELAUNCH;
   const int n = (int)(n_total < MAX_NMS ? n_total : MAX_NMS);
   const int W = (n + 63) / 64;
   float* det = (float*)(base + L.det);
@@ -264,11 +264,10 @@ extern "C" int sodt_nms_select(const float* z, int nc, const unsigned long long*
   int* nkeep = (int*)(base + L.nkeep);
   float* rows = (float*)(base + L.rows);
   int* valid = (int*)(base + L.valid);
-  nms_gather_kernel<<<(n + 255) / 256, 256, 0, stream>>>(z, ks, n, nc, agnostic, det, boxes);
-  nms_mask_kernel<<<dim3(W, W), 64, 0, stream>>>(boxes, n, W, iou_thres, mask);
-  nms_reduce_kernel<<<1, 512, 0, stream>>>(mask, n, W, MAX_DET, keep, nkeep);
+  if (int err = sodt_launch<nms_gather_kernel>(dim3((n + 255) / 256), dim3(256), 0, stream, z, ks, n, nc, agnostic, det, boxes)) return err;
+  if (int err = sodt_launch<nms_mask_kernel>(dim3(W, W), dim3(64), 0, stream, boxes, n, W, iou_thres, mask)) return err;
+  if (int err = sodt_launch<nms_reduce_kernel>(dim3(1), dim3(512), 0, stream, mask, n, W, MAX_DET, keep, nkeep)) return err;
   const int merge = n_total > 1 && n_total < 3000;   // general.py:500 tests the pre-truncation count
-  nms_merge_kernel<<<MAX_DET, 64, 0, stream>>>(det, boxes, n, keep, nkeep, iou_thres, merge, rows, valid);
-  nms_compact_kernel<<<1, 64, 0, stream>>>(rows, valid, keep, ks, nkeep, out, out_index, out_count);
-  return SODT_OK;
+  if (int err = sodt_launch<nms_merge_kernel>(MAX_DET, dim3(64), 0, stream, det, boxes, n, keep, nkeep, iou_thres, merge, rows, valid)) return err;
+  return sodt_launch<nms_compact_kernel>(dim3(1), dim3(64), 0, stream, rows, valid, keep, ks, nkeep, out, out_index, out_count);
 }

@@ -2,6 +2,7 @@
 // 16-byte loads, wave-64 shuffle reductions, two-pass variance from registers).
 // Reference ops: nn.LayerNorm(C), eps 1e-5 (backbone_vit.py:1048,1054,837).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -243,17 +244,15 @@ extern "C" int sodt_layernorm_fwd(const void* x, const float* gamma, const float
   if (C / kpl <= 32) {
     long hb = ((long)M + 7) / 8;
     if (hb > 4096) hb = 4096;
-    if (dtype == SODT_BF16) hipLaunchKernelGGL(ln_fwd_half_kernel<bf16>, dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const bf16*)x, gamma, beta, (bf16*)y, stats, M, C);
-    else hipLaunchKernelGGL(ln_fwd_half_kernel<float>, dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const float*)x, gamma, beta, (float*)y, stats, M, C);
-    return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    if (dtype == SODT_BF16) return sodt_launch<ln_fwd_half_kernel<bf16>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const bf16*)x, gamma, beta, (bf16*)y, stats, M, C);
+    return sodt_launch<ln_fwd_half_kernel<float>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const float*)x, gamma, beta, (float*)y, stats, M, C);
   }
   const int nc = (C / kpl + 63) / 64;
-#define LNF(TY, NC) hipLaunchKernelGGL((ln_fwd_kernel<TY, NC>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
+#define LNF(TY, NC) sodt_launch<ln_fwd_kernel<TY, NC>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
                        (const TY*)x, gamma, beta, (TY*)y, stats, M, C)
-  if (dtype == SODT_BF16) { if (nc == 1) LNF(bf16, 1); else if (nc == 2) LNF(bf16, 2); else LNF(bf16, 4); }
-  else { if (nc == 1) LNF(float, 1); else if (nc == 2) LNF(float, 2); else LNF(float, 4); }
+  if (dtype == SODT_BF16) return nc == 1 ? LNF(bf16, 1) : nc == 2 ? LNF(bf16, 2) : LNF(bf16, 4);
+  return nc == 1 ? LNF(float, 1) : nc == 2 ? LNF(float, 2) : LNF(float, 4);
 #undef LNF
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_layernorm_bwd(const void* dy, const void* x, const float* stats, const float* gamma,
@@ -267,15 +266,13 @@ extern "C" int sodt_layernorm_bwd(const void* dy, const void* x, const float* st
   if (C / kpl <= 32) {
     long hb = ((long)M + 7) / 8;
     if (hb > 1024) hb = 1024;
-    if (dtype == SODT_BF16) hipLaunchKernelGGL(ln_bwd_half_kernel<bf16>, dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, (const bf16*)x, stats, gamma, (const bf16*)dres, (bf16*)dx, dgamma, dbeta, M, C);
-    else hipLaunchKernelGGL(ln_bwd_half_kernel<float>, dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const float*)dy, (const float*)x, stats, gamma, (const float*)dres, (float*)dx, dgamma, dbeta, M, C);
-    return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    if (dtype == SODT_BF16) return sodt_launch<ln_bwd_half_kernel<bf16>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, (const bf16*)x, stats, gamma, (const bf16*)dres, (bf16*)dx, dgamma, dbeta, M, C);
+    return sodt_launch<ln_bwd_half_kernel<float>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const float*)dy, (const float*)x, stats, gamma, (const float*)dres, (float*)dx, dgamma, dbeta, M, C);
   }
   const int nc = (C / kpl + 63) / 64;
-#define LNB(TY, NC) hipLaunchKernelGGL((ln_bwd_kernel<TY, NC>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
+#define LNB(TY, NC) sodt_launch<ln_bwd_kernel<TY, NC>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
                        (const TY*)dy, (const TY*)x, stats, gamma, (const TY*)dres, (TY*)dx, dgamma, dbeta, M, C)
-  if (dtype == SODT_BF16) { if (nc == 1) LNB(bf16, 1); else if (nc == 2) LNB(bf16, 2); else LNB(bf16, 4); }
-  else { if (nc == 1) LNB(float, 1); else if (nc == 2) LNB(float, 2); else LNB(float, 4); }
+  if (dtype == SODT_BF16) return nc == 1 ? LNB(bf16, 1) : nc == 2 ? LNB(bf16, 2) : LNB(bf16, 4);
+  return nc == 1 ? LNB(float, 1) : nc == 2 ? LNB(float, 2) : LNB(float, 4);
 #undef LNB
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }

@@ -42,6 +42,7 @@
 // sqrt(1 - b2^t) are then formed in the kernel, in double from the double hyper-parameters (the reason is the one above),
 // once per thread: lane l of each group of eight forms one of the eight values and the wave shares them.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -265,11 +266,10 @@ static int sgd_launch(float* p, const float* g, float* mom, float* ema, void* p_
   const bool bf = p_cast && cast_dtype == SODT_BF16;
   if (!bf && p_cast && cast_dtype != SODT_F32) return SODT_EINVAL;
 #define SODT_SGD_LAUNCH(TC, CTL) \
-  hipLaunchKernelGGL((sgd_ema_kernel<TC, CTL>), dim3((unsigned)nb), dim3(256), 0, s, p, g, mom, ema, (TC*)p_cast, group_of_chunk, nchunk, h, ctl)
-  if (ctl) { if (bf) SODT_SGD_LAUNCH(bf16, true); else SODT_SGD_LAUNCH(float, true); }
-  else     { if (bf) SODT_SGD_LAUNCH(bf16, false); else SODT_SGD_LAUNCH(float, false); }
+  sodt_launch<sgd_ema_kernel<TC, CTL>>(dim3((unsigned)nb), dim3(256), 0, s, p, g, mom, ema, (TC*)p_cast, group_of_chunk, nchunk, h, ctl)
+  if (ctl) return bf ? SODT_SGD_LAUNCH(bf16, true) : SODT_SGD_LAUNCH(float, true);
+  return bf ? SODT_SGD_LAUNCH(bf16, false) : SODT_SGD_LAUNCH(float, false);
 #undef SODT_SGD_LAUNCH
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_sgd_ema_step(float* p, const float* g, float* mom, float* ema, void* p_cast, int cast_dtype,
@@ -320,12 +320,11 @@ static int adam_launch(float* p, const float* g, float* exp_avg, float* exp_avg_
   const bool bf = p_cast && cast_dtype == SODT_BF16;
   if (!bf && p_cast && cast_dtype != SODT_F32) return SODT_EINVAL;
 #define SODT_ADAM_LAUNCH(TC, CTL)                                                                                            \
-  hipLaunchKernelGGL((adam_ema_kernel<TC, CTL>), dim3((unsigned)nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, ema, (TC*)p_cast, \
+  sodt_launch<adam_ema_kernel<TC, CTL>>(dim3((unsigned)nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, ema, (TC*)p_cast, \
                      group_of_chunk, nchunk, h, ca)
-  if (ctl) { if (bf) SODT_ADAM_LAUNCH(bf16, true); else SODT_ADAM_LAUNCH(float, true); }
-  else     { if (bf) SODT_ADAM_LAUNCH(bf16, false); else SODT_ADAM_LAUNCH(float, false); }
+  if (ctl) return bf ? SODT_ADAM_LAUNCH(bf16, true) : SODT_ADAM_LAUNCH(float, true);
+  return bf ? SODT_ADAM_LAUNCH(bf16, false) : SODT_ADAM_LAUNCH(float, false);
 #undef SODT_ADAM_LAUNCH
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_adam_ema_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* ema, void* p_cast,
@@ -358,8 +357,7 @@ extern "C" int sodt_grad_stats(const float* g, const unsigned char* group_of_chu
   if (nb > 1024) nb = 1024;
   hipStream_t s = (hipStream_t)st;
   // the three words the blocks share (acc_sumsq, acc_found, ticket: the record's first 16 bytes) start every call at zero
-  if (hipMemsetAsync(ctl, 0, 16, s) != hipSuccess) return SODT_EINVAL;
-  hipLaunchKernelGGL(grad_stats_kernel, dim3((unsigned)nb), dim3(256), 0, s, g, group_of_chunk, nchunk, scale, found_inf_in,
+  if (hipMemsetAsync(ctl, 0, 16, s) != hipSuccess) return SODT_ELAUNCH;
+  return sodt_launch<grad_stats_kernel>(dim3((unsigned)nb), dim3(256), 0, s, g, group_of_chunk, nchunk, scale, found_inf_in,
                      grad_scale, max_norm, skip_nonfinite, ctl);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }

@@ -7,6 +7,7 @@
 // outputs whose recorded argmax points at it - no atomics, deterministic.  HBM-bound, small (the SPP runs on the stride-16
 // map: B x (S/16)^2 tokens).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -95,10 +96,9 @@ extern "C" int sodt_maxpool5_fwd(const void* x, int ldx, void* y, int ldy, unsig
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % kpl) || (ldx % kpl) || (ldy % kpl)) return SODT_EINVAL;
   const unsigned gr = pool_blocks((long)B * H * W * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(maxpool5_fwd_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)x, ldx, (bf16*)y, ldy, argmax, B, H, W, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(maxpool5_fwd_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)x, ldx, (float*)y, ldy, argmax, B, H, W, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<maxpool5_fwd_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)x, ldx, (bf16*)y, ldy, argmax, B, H, W, C);
+  if (dtype == SODT_F32) return sodt_launch<maxpool5_fwd_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)x, ldx, (float*)y, ldy, argmax, B, H, W, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_maxpool5_bwd(const void* dy, int lddy, const unsigned char* argmax, void* dx, int lddx, int accumulate,
@@ -106,8 +106,7 @@ extern "C" int sodt_maxpool5_bwd(const void* dy, int lddy, const unsigned char* 
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!dy || !dx || !argmax || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % kpl) || (lddx % kpl) || (lddy % kpl)) return SODT_EINVAL;
   const unsigned gr = pool_blocks((long)B * H * W * (C / kpl));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(maxpool5_bwd_kernel<bf16>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, argmax, (bf16*)dx, lddx, accumulate, B, H, W, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(maxpool5_bwd_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, argmax, (float*)dx, lddx, accumulate, B, H, W, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<maxpool5_bwd_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, argmax, (bf16*)dx, lddx, accumulate, B, H, W, C);
+  if (dtype == SODT_F32) return sodt_launch<maxpool5_bwd_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, argmax, (float*)dx, lddx, accumulate, B, H, W, C);
+  return SODT_EINVAL;
 }

@@ -16,6 +16,7 @@
 // output pixels of one plane (one 16-byte store); its 2 x (up to 10) source bytes are two rows of one cache line region,
 // read through L1 by neighbouring lanes.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -80,6 +81,5 @@ extern "C" int sodt_preprocess_u8(const unsigned char* rgb, const unsigned char*
   const long total = (long)Hout * ((Wout + 3) / 4) * (a.planes[0] + a.planes[1]);
   long blocks = (total + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(preprocess_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, a);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<preprocess_u8_kernel>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, a);
 }

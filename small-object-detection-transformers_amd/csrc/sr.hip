@@ -3,6 +3,7 @@
 // align_corners=True and its adjoint, PixelShuffle(2) and its adjoint, gradient accumulation, and the (B, C, H, W) f32 <->
 // token-major conversion of the branch's output at the model boundary.  All HBM-bound, 16-byte accesses, grid-stride.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -187,60 +188,53 @@ static bool sr_ok(const void* a, const void* b, int B, int H, int W, int C, int 
 extern "C" int sodt_bilinear_up2_fwd(const void* x, void* y, int ldy, int B, int H, int W, int C, int dtype, sodt_stream_t st) {
   if (!sr_ok(x, y, B, H, W, C, dtype) || ldy < C || (ldy % (dtype == SODT_BF16 ? 8 : 4))) return SODT_EINVAL;
   const long n = (long)B * 4 * H * W * (C / (dtype == SODT_BF16 ? 8 : 4));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(bilinear_up2_fwd_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)x, (bf16*)y, ldy, B, H, W, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(bilinear_up2_fwd_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)x, (float*)y, ldy, B, H, W, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<bilinear_up2_fwd_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)x, (bf16*)y, ldy, B, H, W, C);
+  if (dtype == SODT_F32) return sodt_launch<bilinear_up2_fwd_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)x, (float*)y, ldy, B, H, W, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_bilinear_up2_bwd(const void* dy, int lddy, void* dx, const void* relu_out, int B, int H, int W, int C, int dtype,
                                      sodt_stream_t st) {
   if (!sr_ok(dy, dx, B, H, W, C, dtype) || !al16(relu_out) || lddy < C || (lddy % (dtype == SODT_BF16 ? 8 : 4))) return SODT_EINVAL;
   const long n = (long)B * H * W * (C / (dtype == SODT_BF16 ? 8 : 4));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(bilinear_up2_bwd_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (bf16*)dx, (const bf16*)relu_out, B, H, W, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(bilinear_up2_bwd_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (float*)dx, (const float*)relu_out, B, H, W, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<bilinear_up2_bwd_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (bf16*)dx, (const bf16*)relu_out, B, H, W, C);
+  if (dtype == SODT_F32) return sodt_launch<bilinear_up2_bwd_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (float*)dx, (const float*)relu_out, B, H, W, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_pixel_shuffle2(const void* in, void* out, int B, int H, int W, int C, int inverse, int dtype, sodt_stream_t st) {
   if (!sr_ok(in, out, B, H, W, C, dtype)) return SODT_EINVAL;
   const long n = (long)B * H * W * (4 * C / (dtype == SODT_BF16 ? 8 : 4));
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(pixel_shuffle2_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)in, (bf16*)out, B, H, W, C, inverse);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(pixel_shuffle2_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)in, (float*)out, B, H, W, C, inverse);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<pixel_shuffle2_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)in, (bf16*)out, B, H, W, C, inverse);
+  if (dtype == SODT_F32) return sodt_launch<pixel_shuffle2_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)in, (float*)out, B, H, W, C, inverse);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_add_rows(void* dst, int ldd, int dcol, const void* src, int lds_, int scol, long M, int C, int dtype, sodt_stream_t st) {
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (dst && src && dtype == SODT_F32 && M == 1 && C > 0 && C < 64 && (C % kpl)) {
     // one short f32 row below the 16-byte granule (the bias gradient of a 3-channel convolution): element-wise
-    hipLaunchKernelGGL(add_small_f32_kernel, dim3(1), dim3(64), 0, (hipStream_t)st, (float*)dst + dcol, (const float*)src + scol, C);
-    return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    return sodt_launch<add_small_f32_kernel>(dim3(1), dim3(64), 0, (hipStream_t)st, (float*)dst + dcol, (const float*)src + scol, C);
   }
   if (!dst || !src || !al16(dst, src) || M <= 0 || C <= 0 || (C % kpl) || (ldd % kpl) || (lds_ % kpl) || (dcol % kpl) || (scol % kpl)) return SODT_EINVAL;
   const long n = M * (C / kpl);
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(add_rows_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (bf16*)dst, ldd, dcol, (const bf16*)src, lds_, scol, M, C);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(add_rows_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (float*)dst, ldd, dcol, (const float*)src, lds_, scol, M, C);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<add_rows_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (bf16*)dst, ldd, dcol, (const bf16*)src, lds_, scol, M, C);
+  if (dtype == SODT_F32) return sodt_launch<add_rows_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (float*)dst, ldd, dcol, (const float*)src, lds_, scol, M, C);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_nchw_f32_from_rows(const void* rows, int ld, float* y, int B, int C, int H, int W, int dtype, sodt_stream_t st) {
   if (!rows || !y || B <= 0 || C <= 0 || C > ld || H <= 0 || W <= 0) return SODT_EINVAL;
   const long n = (long)B * C * H * W;
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(nchw_from_rows_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)rows, ld, y, B, C, H * W);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(nchw_from_rows_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)rows, ld, y, B, C, H * W);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<nchw_from_rows_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const bf16*)rows, ld, y, B, C, H * W);
+  if (dtype == SODT_F32) return sodt_launch<nchw_from_rows_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, (const float*)rows, ld, y, B, C, H * W);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_rows_from_nchw_f32(const float* y, void* rows, int ld, int B, int C, int H, int W, int dtype, sodt_stream_t st) {
   if (!rows || !y || B <= 0 || C <= 0 || C > ld || H <= 0 || W <= 0) return SODT_EINVAL;
   const long n = (long)B * H * W * ld;
-  if (dtype == SODT_BF16) hipLaunchKernelGGL(rows_from_nchw_kernel<bf16>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, y, (bf16*)rows, ld, B, C, H * W);
-  else if (dtype == SODT_F32) hipLaunchKernelGGL(rows_from_nchw_kernel<float>, dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, y, (float*)rows, ld, B, C, H * W);
-  else return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  if (dtype == SODT_BF16) return sodt_launch<rows_from_nchw_kernel<bf16>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, y, (bf16*)rows, ld, B, C, H * W);
+  if (dtype == SODT_F32) return sodt_launch<rows_from_nchw_kernel<float>>(dim3(nblk(n)), dim3(256), 0, (hipStream_t)st, y, (float*)rows, ld, B, C, H * W);
+  return SODT_EINVAL;
 }

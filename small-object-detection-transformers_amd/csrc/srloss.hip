@@ -23,6 +23,7 @@
 // the GradScaler scale, the world size and the --quad factor of Train.py:439-445).
 // HBM-bound: 4 B + 1 B read per element forward, 4 B + 1 B read and 4 B written backward.
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -236,16 +237,15 @@ extern "C" int sodt_sr_l1_workspace_bytes(int B, int C, int H, int W, size_t* by
   return SODT_OK;
 }
 
+// (returns from the calling entry point)
 #define SODT_SR_L1_DISPATCH(KERNEL, ...)                                                                                        \
   do {                                                                                                                          \
     const dim3 grid(pl.bx, pl.planes), block(256);                                                                              \
-    if (target_dtype == SODT_U8) {                                                                                              \
-      if (pl.vec) hipLaunchKernelGGL((KERNEL<unsigned char, true>), grid, block, 0, s, __VA_ARGS__);                            \
-      else hipLaunchKernelGGL((KERNEL<unsigned char, false>), grid, block, 0, s, __VA_ARGS__);                                  \
-    } else {                                                                                                                    \
-      if (pl.vec) hipLaunchKernelGGL((KERNEL<float, true>), grid, block, 0, s, __VA_ARGS__);                                    \
-      else hipLaunchKernelGGL((KERNEL<float, false>), grid, block, 0, s, __VA_ARGS__);                                          \
-    }                                                                                                                           \
+    if (target_dtype == SODT_U8)                                                                                                \
+      return pl.vec ? sodt_launch<KERNEL<unsigned char, true>>(grid, block, 0, s, __VA_ARGS__)                                  \
+                    : sodt_launch<KERNEL<unsigned char, false>>(grid, block, 0, s, __VA_ARGS__);                                \
+    return pl.vec ? sodt_launch<KERNEL<float, true>>(grid, block, 0, s, __VA_ARGS__)                                            \
+                  : sodt_launch<KERNEL<float, false>>(grid, block, 0, s, __VA_ARGS__);                                          \
   } while (0)
 
 extern "C" int sodt_sr_l1_fwd(const float* sr, const void* rgb, const void* ir, int target_dtype, int mode, int B, int C,
@@ -255,11 +255,10 @@ extern "C" int sodt_sr_l1_fwd(const float* sr, const void* rgb, const void* ir, 
   if (!ws || ((uintptr_t)ws & 15) || !loss || ((uintptr_t)loss & 3)) return SODT_EINVAL;
   if (ws_bytes < 16 + sizeof(double) * (size_t)pl.bx * pl.planes) return SODT_EINVAL;
   hipStream_t s = (hipStream_t)st;
-  if (hipMemsetAsync(ws, 0, 16, s) != hipSuccess) return SODT_EINVAL;       // the ticket starts every call at zero
+  if (hipMemsetAsync(ws, 0, 16, s) != hipSuccess) return SODT_ELAUNCH;       // the ticket starts every call at zero
   unsigned* ticket = (unsigned*)ws;
   double* part = (double*)((char*)ws + 16);
   SODT_SR_L1_DISPATCH(sr_l1_fwd_kernel, pl.a, pl.w, pl.n0, pl.n1, ticket, part, loss);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 
 extern "C" int sodt_sr_l1_bwd(const float* sr, const void* rgb, const void* ir, int target_dtype, int mode, int B, int C,
@@ -275,6 +274,5 @@ extern "C" int sodt_sr_l1_bwd(const float* sr, const void* rgb, const void* ir, 
   hipStream_t s = (hipStream_t)st;
   const double wn0 = pl.w / pl.n0, wn1 = pl.n1 > 0.0 ? pl.w / pl.n1 : 0.0;
   SODT_SR_L1_DISPATCH(sr_l1_bwd_kernel, pl.a, upstream, wn0, wn1, dsr);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
 }
 #undef SODT_SR_L1_DISPATCH

@@ -20,6 +20,7 @@
 #pragma clang fp contract(off)
 #include <rocprim/device/device_radix_sort.hpp>
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -352,9 +353,9 @@ int layout(int B, long cap, ws_layout& L) {
   const size_t P = (size_t)B * cap;
   size_t t64 = 0, t32 = 0;
   if (rocprim::radix_sort_pairs<rocprim::default_config, const uint64_t*, uint64_t*, const uint32_t*, uint32_t*>(
-          nullptr, t64, nullptr, nullptr, nullptr, nullptr, P, 0, 64, 0) != hipSuccess) return SODT_EINVAL;
+          nullptr, t64, nullptr, nullptr, nullptr, nullptr, P, 0, 64, 0) != hipSuccess) return SODT_ELAUNCH;
   if (rocprim::radix_sort_pairs<rocprim::default_config, const uint32_t*, uint32_t*, const uint32_t*, uint32_t*>(
-          nullptr, t32, nullptr, nullptr, nullptr, nullptr, P, 0, 32, 0) != hipSuccess) return SODT_EINVAL;
+          nullptr, t32, nullptr, nullptr, nullptr, nullptr, P, 0, 32, 0) != hipSuccess) return SODT_ELAUNCH;
   size_t o = 0;
   auto take = [&](size_t& f, size_t bytes) { f = o; o += align256(bytes); };
   take(L.k64a, P * 8); take(L.k64b, P * 8); take(L.skey, P * 8);
@@ -378,10 +379,9 @@ extern "C" int sodt_wbf_candidates(const float* z, int B, int N, int nc, float c
   if (!z || !boxes || !scores || !labels || !src || !counts || B <= 0 || B > MAX_B || N <= 0 || nc <= 0 ||
       (long)B * N > (1L << 30) || misaligned(boxes, 16))
     return SODT_EINVAL;
-  if (hipMemsetAsync(counts, 0, sizeof(int) * B, stream) != hipSuccess) return SODT_EINVAL;
-  wbf_candidates_kernel<<<dim3((N + 255) / 256, B), 256, 0, stream>>>(z, N, nc, conf_thres, image_size, (float4*)boxes, scores,
+  if (hipMemsetAsync(counts, 0, sizeof(int) * B, stream) != hipSuccess) return SODT_ELAUNCH;
+  return sodt_launch<wbf_candidates_kernel>(dim3((N + 255) / 256, B), dim3(256), 0, stream, z, N, nc, conf_thres, image_size, (float4*)boxes, scores,
                                                                      labels, src, counts);
-  return SODT_OK;
 }
 
 extern "C" int sodt_wbf_fuse_workspace_bytes(int B, long cap, size_t* bytes) {
@@ -425,47 +425,45 @@ extern "C" int sodt_wbf_fuse(const float* boxes, const float* scores, const int*
   const wbf_in in{scores, labels, model, counts, cap, skip_box_thr, n_models};
   const unsigned nb = (unsigned)((P + 255) / 256);
 
-  if (hipMemsetAsync(cl.n, 0, (size_t)P * 4, stream) != hipSuccess) return SODT_EINVAL;
-  if (hipMemsetAsync(out_counts, 0, sizeof(int) * B, stream) != hipSuccess) return SODT_EINVAL;
+  if (hipMemsetAsync(cl.n, 0, (size_t)P * 4, stream) != hipSuccess) return SODT_ELAUNCH;
+  if (hipMemsetAsync(out_counts, 0, sizeof(int) * B, stream) != hipSuccess) return SODT_ELAUNCH;
   // order: label, then descending weighted score, then ascending source index (three stable passes, last key first)
   const uint32_t* order = v32a;
   if (src) {
-    wbf_key_src_kernel<<<nb, 256, 0, stream>>>(src, P, k32a, v32a);
+    if (int err = sodt_launch<wbf_key_src_kernel>(nb, dim3(256), 0, stream, src, P, k32a, v32a)) return err;
     if (rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)k32a, k32b, (const uint32_t*)v32a, v32b, (size_t)P, 0, 32, stream) !=
-        hipSuccess) return SODT_EINVAL;
+        hipSuccess) return SODT_ELAUNCH;
     order = v32b;
   } else {
-    wbf_key_src_kernel<<<nb, 256, 0, stream>>>(nullptr, P, nullptr, v32a);
+    if (int err = sodt_launch<wbf_key_src_kernel>(nb, dim3(256), 0, stream, nullptr, P, nullptr, v32a)) return err;
   }
   uint32_t* order2 = order == v32a ? v32b : v32a;
-  wbf_key_score_kernel<<<nb, 256, 0, stream>>>(in, W, order, P, k64a);
+  if (int err = sodt_launch<wbf_key_score_kernel>(nb, dim3(256), 0, stream, in, W, order, P, k64a)) return err;
   tb = L.sort_tmp_bytes;
   if (rocprim::radix_sort_pairs(tmp, tb, (const uint64_t*)k64a, k64b, order, order2, (size_t)P, 0, 64, stream) != hipSuccess)
-    return SODT_EINVAL;
-  wbf_key_seg_kernel<<<nb, 256, 0, stream>>>(in, order2, P, k64a);
+    return SODT_ELAUNCH;
+  if (int err = sodt_launch<wbf_key_seg_kernel>(nb, dim3(256), 0, stream, in, order2, P, k64a)) return err;
   tb = L.sort_tmp_bytes;
   if (rocprim::radix_sort_pairs(tmp, tb, (const uint64_t*)k64a, skey, (const uint32_t*)order2, perm, (size_t)P, 0, 64, stream) !=
-      hipSuccess) return SODT_EINVAL;
-  wbf_gather_kernel<<<nb, 256, 0, stream>>>(in, W, (const float4*)boxes, skey, perm, P, sbox, ss, sw, smodel);
+      hipSuccess) return SODT_ELAUNCH;
+  if (int err = sodt_launch<wbf_gather_kernel>(nb, dim3(256), 0, stream, in, W, (const float4*)boxes, skey, perm, P, sbox, ss, sw, smodel)) return err;
 
   const dim3 grid((unsigned)(cap < 64 ? cap : 64), (unsigned)B);
-  if (scan_lanes == 256)
-    wbf_cluster_kernel<256><<<grid, 256, 0, stream>>>(skey, P, sbox, ss, sw, smodel, W, iou_thr, conf_type, allows_overflow, cl,
-                                                      assign, out_counts);
-  else
-    wbf_cluster_kernel<64><<<grid, 64, 0, stream>>>(skey, P, sbox, ss, sw, smodel, W, iou_thr, conf_type, allows_overflow, cl,
-                                                    assign, out_counts);
+  if (int err = scan_lanes == 256
+          ? sodt_launch<wbf_cluster_kernel<256>>(grid, dim3(256), 0, stream, skey, P, sbox, ss, sw, smodel, W, iou_thr, conf_type, allows_overflow, cl,
+                                                 assign, out_counts)
+          : sodt_launch<wbf_cluster_kernel<64>>(grid, dim3(64), 0, stream, skey, P, sbox, ss, sw, smodel, W, iou_thr, conf_type, allows_overflow, cl,
+                                                assign, out_counts)) return err;
 
   // output order: image, then descending score, then label, then creation order (the slot order)
-  wbf_okey_score_kernel<<<nb, 256, 0, stream>>>(cl, P, k64a, v32a);
+  if (int err = sodt_launch<wbf_okey_score_kernel>(nb, dim3(256), 0, stream, cl, P, k64a, v32a)) return err;
   tb = L.sort_tmp_bytes;
   if (rocprim::radix_sort_pairs(tmp, tb, (const uint64_t*)k64a, k64b, (const uint32_t*)v32a, v32b, (size_t)P, 0, 64, stream) !=
-      hipSuccess) return SODT_EINVAL;
-  wbf_okey_image_kernel<<<nb, 256, 0, stream>>>(cl, skey, v32b, P, k32a);
+      hipSuccess) return SODT_ELAUNCH;
+  if (int err = sodt_launch<wbf_okey_image_kernel>(nb, dim3(256), 0, stream, cl, skey, v32b, P, k32a)) return err;
   tb = L.sort_tmp_bytes;
   if (rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)k32a, k32b, (const uint32_t*)v32b, v32a, (size_t)P, 0, 32, stream) !=
-      hipSuccess) return SODT_EINVAL;
-  wbf_output_kernel<<<nb, 256, 0, stream>>>(cl, skey, v32a, k32b, P, cap, (float4*)out_boxes, out_scores, out_labels, rank);
-  if (member) wbf_member_kernel<<<nb, 256, 0, stream>>>(skey, perm, assign, rank, P, member);
-  return SODT_OK;
+      hipSuccess) return SODT_ELAUNCH;
+  if (int err = sodt_launch<wbf_output_kernel>(nb, dim3(256), 0, stream, cl, skey, v32a, k32b, P, cap, (float4*)out_boxes, out_scores, out_labels, rank)) return err;
+  return member ? sodt_launch<wbf_member_kernel>(nb, dim3(256), 0, stream, skey, perm, assign, rank, P, member) : SODT_OK;
 }

@@ -40,6 +40,7 @@
 //   (b * nwy + wy) * nwx + wx after the cyclic shift, token = window-local row-major): the layout the attention
 //   backward stages into LDS anyway (sodt_window_attn_bwd_wm), 6 KB contiguous per (window, head).
 #include "common.h"
+#include "launch.h"
 #include "../../include/sodt_hip.h"
 #include <type_traits>
 #include <cstdlib>
@@ -641,19 +642,9 @@ int launch_block(const WArgs& a, hipStream_t st) {
   using L = WL<T>;
   constexpr int LDS = NWV * L::XNB + NST * L::STAGE + NWV * L::VPB + 5 * WC * 4;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  auto kern = wmsa_block_kernel<T, NWV, NST, SAVE, STAMP>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
   const int nquads = (a.nwin + NWV - 1) / NWV;
   const int grid = nquads < 256 ? nquads : 256;          // one workgroup per CU, persistent over the window groups
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), LDS, st, a);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<wmsa_block_kernel<T, NWV, NST, SAVE, STAMP>>(dim3(grid), dim3(NWV * 64), LDS, st, a);
 }
 
 bool wmsa_shape_ok(int B, int H, int W, int C, int heads, int ws, int shift) {
@@ -675,14 +666,12 @@ extern "C" int sodt_wmsa_pack(const float* qkv_w, const float* qkv_b, const floa
   if (C != WC || heads != WHEADS || ws != WWS) return SODT_EINVAL;
   hipStream_t st = (hipStream_t)st_;
   if (dtype == SODT_BF16)
-    hipLaunchKernelGGL(wmsa_pack_kernel<bf16>, dim3(WHEADS + 8), dim3(256), 0, st, qkv_w, qkv_b, proj_w, proj_b, rpb_table,
-                       n1_w, n1_b, n2_w, n2_b, (unsigned char*)wpk);
-  else if (dtype == SODT_F32)
-    hipLaunchKernelGGL(wmsa_pack_kernel<float>, dim3(WHEADS + 8), dim3(256), 0, st, qkv_w, qkv_b, proj_w, proj_b, rpb_table,
-                       n1_w, n1_b, n2_w, n2_b, (unsigned char*)wpk);
-  else
-    return SODT_EINVAL;
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+    return sodt_launch<wmsa_pack_kernel<bf16>>(dim3(WHEADS + 8), dim3(256), 0, st, qkv_w, qkv_b, proj_w, proj_b, rpb_table,
+                                               n1_w, n1_b, n2_w, n2_b, (unsigned char*)wpk);
+  if (dtype == SODT_F32)
+    return sodt_launch<wmsa_pack_kernel<float>>(dim3(WHEADS + 8), dim3(256), 0, st, qkv_w, qkv_b, proj_w, proj_b, rpb_table,
+                                                n1_w, n1_b, n2_w, n2_b, (unsigned char*)wpk);
+  return SODT_EINVAL;
 }
 
 extern "C" int sodt_wmsa_block_fwd(const void* x, const void* wpk, void* xm, void* xn2, float* st1, float* st2,
@@ -717,6 +706,6 @@ extern "C" int sodt_wmsa_block_fwd(const void* x, const void* wpk, void* xm, voi
  * workgroup of the last such launch: [barrier wait, QKV, pack/save, S+softmax, PV+proj, stage store, prologue, epilogue] */
 extern "C" int sodt_debug_wmsa_stamps(long long* out, int enable) {
   g_wmsa_stamp_enable = enable != 0;
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wmsa_stamps), sizeof(long long) * 256 * 8) != hipSuccess) return SODT_EINVAL;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wmsa_stamps), sizeof(long long) * 256 * 8) != hipSuccess) return SODT_ELAUNCH;
   return SODT_OK;
 }

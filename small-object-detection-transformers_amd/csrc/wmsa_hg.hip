@@ -25,6 +25,7 @@
 //
 // LDS: 2 x 24 KB tiles + 72 KB weights + 25.5 KB tables + 3.75 KB vectors = 149.25 KB.
 #include "wmsa_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -593,19 +594,9 @@ bool g_hg_stamp_enable = false;
 template <bool SAVE, bool STAMP = false>
 int hg_launch(const WArgs& a, hipStream_t st) {
   constexpr int LDS = SAVE ? HG_LDS_SAVE : HG_LDS_INF;
-  static bool attr_set = false;
-  auto kern = wmsa_hg_kernel<SAVE, STAMP>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      return SODT_EINVAL;
-    }
-    attr_set = true;
-  }
   const int npairs = (a.nwin + 1) / 2;
   const int grid = npairs < 256 ? npairs : 256;          // one workgroup per CU, persistent over the window pairs
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, a);
-  return hipGetLastError() == hipSuccess ? SODT_OK : SODT_EINVAL;
+  return sodt_launch<wmsa_hg_kernel<SAVE, STAMP>>(dim3(grid), dim3(512), LDS, st, a);
 }
 
 }  // namespace
@@ -621,6 +612,6 @@ int wmsa_hg_launch(const WArgs& a, bool save, hipStream_t st) {
  * residual loads + staging + B9, epilogue] */
 extern "C" int sodt_debug_wmsa_hg_stamps(long long* out, int enable) {
   g_hg_stamp_enable = enable != 0;
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hg_stamps), sizeof(long long) * 512 * 12) != hipSuccess) return SODT_EINVAL;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hg_stamps), sizeof(long long) * 512 * 12) != hipSuccess) return SODT_ELAUNCH;
   return SODT_OK;
 }

@@ -315,7 +315,7 @@ def linear_bwd_sq(dY: torch.Tensor, X: torch.Tensor, wT: torch.Tensor, dX: torch
     fn = _lib.sodt_linear_bwd_sq
     args = (C.byref(g), L.BF16)
     rc = fn(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc == 1:                     # SODT_EINVAL: validated before any launch
+    if rc == L.EINVAL:              # refused before any launch (a failed launch is SODT_ELAUNCH and raises below)
         return False
     if rc != 0:
         raise RuntimeError(f"sodt_linear_bwd_sq failed with status {rc}")
@@ -829,7 +829,8 @@ def maxpool5_bwd(dy, argmax, dx, B, H, W, Cc, lddy=None, lddx=None, dy_off=0, dx
 
 
 def gemm_set_variant(v) -> None:
-    """0/False: automatic; 1/True: force the K-loop tile kernel; 2: force the A-stationary kernel (tests)."""
+    """Test hook (SODT_VARIANT_* in include/sodt_hip.h).  0/False: automatic; 1/True: the K-loop NT and the 128 x 128 TN kernel;
+    2: A-stationary NT instead of B-stationary, no pipelined kernel; 3: NT as automatic, TN without the pipelined kernel."""
     _lib.sodt_gemm_set_variant(int(v))
 
 

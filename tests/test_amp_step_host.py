@@ -122,6 +122,6 @@ def test_entries_refuse_null_and_misaligned_control_pointers(pkg):
                stats(found=base[4] + 1), stats(gs=float("nan")), stats(mx=float("nan")),
                sgd(None), sgd(ctl + 4), sgd(ctl + 8), adam(None), adam(ctl + 8)):
         assert rc != 0
-    common = open(os.path.join(ROOT, PKG, "csrc", "common.h")).read()
+    common = open(os.path.join(ROOT, "include", "sodt_hip.h")).read()
     einval = int(re.search(r"#define\s+SODT_EINVAL\s+(-?\d+)", common).group(1))
     assert stats(cp=None) == einval and sgd(ctl + 8) == einval and adam(None) == einval

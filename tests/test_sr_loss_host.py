@@ -103,7 +103,7 @@ def test_entries_refuse_bad_arguments_before_a_launch(pkg):
 
     def bwd(sr=sr, ir=ir, code=L.U8, mode=2, Cx=Cc, c_rgb=3, up=scal, d=dsr):
         return lib.sodt_sr_l1_bwd(sr, rgb, ir, code, mode, B, Cx, c_rgb, 1, H, W, up, d, None)
-    common = open(os.path.join(ROOT, PKG, "csrc", "common.h")).read()
+    common = open(os.path.join(ROOT, "include", "sodt_hip.h")).read()
     einval = int(re.search(r"#define\s+SODT_EINVAL\s+(-?\d+)", common).group(1))
     for rc in (fwd(sr=None), fwd(sr=sr + 2), fwd(rgb=None), fwd(ir=None), fwd(code=L.BF16), fwd(code=L.F32, rgb=rgb + 1),
                fwd(mode=3), fwd(mode=-1), fwd(mode=0), fwd(mode=1), fwd(Cx=3), fwd(Cx=5), fwd(c_rgb=1), fwd(c_ir=0), fwd(Hx=0),
