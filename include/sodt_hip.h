@@ -600,6 +600,17 @@ int sodt_adam_ema_step_ctl(float* p, const float* g, float* exp_avg, float* exp_
 int sodt_preprocess_u8(const unsigned char* rgb, const unsigned char* ir, float* out_rgb, float* out_ir, int B, int c_rgb,
                        int c_ir, int Hin, int Win, int Hout, int Wout, sodt_stream_t st);
 
+/* Multi-scale training (csrc/multiscale.hip): the pre-processing above followed by the resize of `--multi-scale`,
+ * `F.interpolate(imgs, size=ns, mode='bilinear', align_corners=False)` (Train.py:396-402), for the RGB and the IR batch in
+ * one launch with no global intermediate and no workspace.  rgb / ir: uint8 (B, c, Hin, Win) contiguous (device); the
+ * align-corners shrink goes to (Hmid, Wmid) (Hmid <= Hin, Wmid <= Win; Hmid == Hin: no shrink), the half-pixel resize from there
+ * to (Hout, Wout), larger or smaller; out_rgb / out_ir: f32 (B, c, Hout, Wout).  Each stage takes its source index and blend
+ * weight from an exact integer quotient and remainder, and the stage-1 values are rounded to f32 as the reference's
+ * intermediate tensor is.  SODT_EINVAL, nothing written: a null pointer, a non-positive size or channel count, Hmid > Hin or
+ * Wmid > Win, or one of Hin * Hmid, Win * Wmid, 2 * Hout * Hmid, 2 * Wout * Wmid, Hin * Win reaching 2^31. */
+int sodt_preprocess_u8_ms(const unsigned char* rgb, const unsigned char* ir, float* out_rgb, float* out_ir, int B, int c_rgb,
+                          int c_ir, int Hin, int Win, int Hmid, int Wmid, int Hout, int Wout, sodt_stream_t st);
+
 /* ComputeLoss.__call__ + build_targets (basics/utils/loss.py:116-224) with bbox_iou(CIoU) (basics/utils/general.py:347-389)
  * for the single detection layer of models/model.yaml: loss values and d(loss * batch) / d pred in one call.
  * pred f32 (B, na, ny, nx, 5+nc) contiguous; targets f32 (nt, 6) = (image, class, x, y, w, h) normalised (device);

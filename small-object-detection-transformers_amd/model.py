@@ -434,6 +434,29 @@ class Model(nn.Module):
         d["_engine"] = None
         return d
 
+    def runs_at(self, S: int) -> bool:
+        """Whether the engine runs a square S x S input on this model: the answer ``multi_scale_size`` needs before it draws a
+        size (Train.py:396-402).  Pure host code - no device, no engine - restating what ``Engine.run``, ``Engine._block_geo`` and
+        ``Engine._block_route`` refuse (tests/test_multiscale_gpu.py holds the two together): S is a multiple of 32; a stage
+        no larger than its window is ONE window, of side 8, 16 or 32 (the attention kernels walk 64-token tiles of whole window
+        rows); the window matches the block's relative-position bias table; and a stage that is not a multiple of its window
+        is zero-padded for unshifted blocks only.  For a model built at 512 or 1024: S = 512 and every multiple of 64 from 576."""
+        if isinstance(S, bool) or not isinstance(S, int) or S <= 0 or S % 32:
+            return False
+        enc = self.image_encoder
+        for stage, H in ((enc.stage1, S // 4), (enc.stage2, S // 8), (enc.stage3, S // 16)):
+            for blk in stage:
+                ws, shift = blk.window_size, blk.shift_size
+                if H <= ws:
+                    ws, shift = H, 0
+                    if ws < 8 or 64 % ws:
+                        return False
+                if blk.attn.relative_position_bias_table.shape[0] != (2 * ws - 1) ** 2:
+                    return False
+                if H % ws and shift > 0:
+                    return False
+        return True
+
     # ------------------------------------------------------------------ forward
     def _get_engine(self):
         if self._engine is None:
