@@ -611,6 +611,26 @@ int sodt_preprocess_u8(const unsigned char* rgb, const unsigned char* ir, float*
 int sodt_preprocess_u8_ms(const unsigned char* rgb, const unsigned char* ir, float* out_rgb, float* out_ir, int B, int c_rgb,
                           int c_ir, int Hin, int Win, int Hmid, int Wmid, int Hout, int Wout, sodt_stream_t st);
 
+/* Quad collate (csrc/quad.hip): the image side of LoadImagesAndLabels.collate_fn4 (basics/utils/datasets.py:637-664, the
+ * loader of `--quad`, Train.py:223).  rgb / ir: uint8 (B, c, H, W) contiguous (device), the SOURCE batch; n = B / 4 groups
+ * of four consecutive samples, samples 4n .. B-1 unused.  Bit g of zoom_mask is the draw of group g (datasets.py:647): set,
+ * the group's image is sample 4g zoomed 2x as `F.interpolate(..., scale_factor=2., mode='bilinear', align_corners=False)`
+ * cast back to uint8 does (datasets.py:648-651), evaluated as the integer expression (9 a + 3 b + 3 c + d) >> 4 that call
+ * equals byte for byte; clear, the four samples tiled 2 x 2, sample 4g+1 BELOW 4g and 4g+2 to its RIGHT (datasets.py:654-655).
+ * The mask travels by value: no device table, no copy, at most 64 groups.  c_ir may be 0 (ir, out_ir then unused).
+ *
+ * sodt_quad_u8 replaces the image outputs of collate_fn4 themselves: out_rgb / out_ir uint8 (n, c, 2H, 2W), what SRLoss
+ * reads under `--super` and what sodt_preprocess_u8_ms resizes under `--multi-scale`.
+ * sodt_preprocess_u8_quad replaces collate_fn4 AND the pre-processing of Train.py:364-374 after it (sodt_preprocess_u8 on the
+ * quad batch, same arithmetic, same bits) in one launch from the source batch, with no uint8 intermediate: out_rgb / out_ir
+ * f32 (n, c, Hout, Wout), Hout <= 2H, Wout <= 2W.
+ * SODT_EINVAL, nothing written: a null pointer, B < 4, B / 4 > 64, a non-positive size or channel count (c_ir < 0), Hout > 2H
+ * or Wout > 2W, or one of 4 * H * W, 2H * Hout, 2W * Wout reaching 2^31. */
+int sodt_quad_u8(const unsigned char* rgb, const unsigned char* ir, unsigned char* out_rgb, unsigned char* out_ir, int B,
+                 int c_rgb, int c_ir, int H, int W, unsigned long long zoom_mask, sodt_stream_t st);
+int sodt_preprocess_u8_quad(const unsigned char* rgb, const unsigned char* ir, float* out_rgb, float* out_ir, int B, int c_rgb,
+                            int c_ir, int H, int W, int Hout, int Wout, unsigned long long zoom_mask, sodt_stream_t st);
+
 /* ComputeLoss.__call__ + build_targets (basics/utils/loss.py:116-224) with bbox_iou(CIoU) (basics/utils/general.py:347-389)
  * for the single detection layer of models/model.yaml: loss values and d(loss * batch) / d pred in one call.
  * pred f32 (B, na, ny, nx, 5+nc) contiguous; targets f32 (nt, 6) = (image, class, x, y, w, h) normalised (device);

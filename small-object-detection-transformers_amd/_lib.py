@@ -167,6 +167,8 @@ SIGNATURES = {
                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _F, _P],
     "sodt_preprocess_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_preprocess_u8_ms": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_quad_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_ulonglong, _P],
+    "sodt_preprocess_u8_quad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_ulonglong, _P],
     "sodt_sr_l1_workspace_bytes": [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     "sodt_sr_l1_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P],
     "sodt_sr_l1_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],

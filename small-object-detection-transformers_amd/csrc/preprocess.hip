@@ -11,12 +11,14 @@
 // remainder of dst * (in - 1) by (out - 1) - one rounding, in the final division - so the result is the correctly rounded
 // evaluation of the same formula: within 1e-6 of the float64 evaluation, and inside ATen-f32's own coordinate noise.
 // out == in is the identity: plain u8 -> f32 / 255.
+// The blend itself is blend.h's sodt_blend4, shared with quad.hip (the two kernels agree bit for bit).
 //
 // HBM-bound byte work (6 MB in, 6.3 MB out per 1024^2 image pair at down_factor 2): one thread produces four consecutive
 // output pixels of one plane (one 16-byte store); its 2 x (up to 10) source bytes are two rows of one cache line region,
 // read through L1 by neighbouring lanes.
 #include "common.h"
 #include "launch.h"
+#include "blend.h"
 #include "../../include/sodt_hip.h"
 
 namespace {
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const PreArgs a) {
       const int x1 = x0 + 1 < a.Win ? x0 + 1 : a.Win - 1;
       const float p00 = (float)r0[x0] / 255.0f, p01 = (float)r0[x1] / 255.0f;
       const float p10 = (float)r1[x0] / 255.0f, p11 = (float)r1[x1] / 255.0f;
-      o[i] = (1.f - ly) * ((1.f - lx) * p00 + lx * p01) + ly * ((1.f - lx) * p10 + lx * p11);
+      o[i] = sodt_blend4(ly, lx, p00, p01, p10, p11);
     }
     if (ox0 + 3 < a.Wout && (((uintptr_t)dp) & 15) == 0) {
       *(float4*)dp = make_float4(o[0], o[1], o[2], o[3]);
