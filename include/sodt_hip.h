@@ -182,6 +182,26 @@ int sodt_window_attn_bwd(const void* qkv, const float* bias_t, const void* out, 
                          int B, int H, int W, int C, int heads, int ws, int shift,
                          int dtype, sodt_stream_t st);
 
+/* The same attention core for a SHIFTED block whose H x W token grid is no multiple of its window (csrc/attention_sp.hip):
+ * SwinTransformerBlock.forward backbone_vit.py:1094-1124 with the zero padding of window_partition / the crop of
+ * window_unpartition :619-672 and the mask of :1058-1077, WindowAttention.forward :968-989.  The reference rolls the unpadded
+ * grid by (-shift, -shift), zero-pads the rolled grid at the bottom / right AFTER norm1 (a pad token's q / k / v are qkv.bias),
+ * attends per window of the padded grid with the mask's region ids taken from the unpadded rolled grid (pad positions: id 0),
+ * crops and rolls back.  qkv [B*H*W][3C], out / dout [B*H*W][C], dqkv [B*H*W][3C] live on the UNPADDED grid in natural token
+ * order; the padded grid is index arithmetic only.  qkv_bias f32 [3C]: what a pad key / value reads, narrowed to the run dtype
+ * as a stored qkv row would be; a pad query is not computed into memory.  lse f32 [B*H*W][heads] (forward: may be NULL for
+ * inference).  bias_t as above.  Accepted geometry: ws == 8, 0 < shift < 8, H > 8, W > 8, at least one of H, W no multiple
+ * of 8, head dim 16 or 32, heads divisible by the waves per workgroup given above; everything else returns SODT_EINVAL and
+ * launches nothing. */
+int sodt_window_attn_sp_fwd(const void* qkv, const float* qkv_bias, const float* bias_t, void* out, float* lse,
+                            int B, int H, int W, int C, int heads, int ws, int shift, int dtype, sodt_stream_t st);
+/* dqkv from dout (recomputes P from lse; `out` is not read and may be NULL), written for every real token.  The k / v gradient
+ * of the pad keys is ADDED to dqkv_bias (f32 [3C]; its q third is never touched); dbias_t accumulates as in
+ * sodt_window_attn_bwd. */
+int sodt_window_attn_sp_bwd(const void* qkv, const float* qkv_bias, const float* bias_t, const void* out, const void* dout,
+                            const float* lse, void* dqkv, float* dqkv_bias, float* dbias_t,
+                            int B, int H, int W, int C, int heads, int ws, int shift, int dtype, sodt_stream_t st);
+
 /* ---- super-resolution auxiliary branch (deeplabedsr.py:35-73): data movement between its convolutions, token-major [B][H][W][C] ----
  * sodt_bilinear_up2_fwd/bwd: F.interpolate(x, size = (2H, 2W), mode = 'bilinear', align_corners = True) (sr_decoder_noBN_noD.py:37) and
  *   its adjoint (dx = sum over the output pixels a source pixel contributes to; written, not accumulated).  y / dy may be a

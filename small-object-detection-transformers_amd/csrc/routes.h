@@ -214,3 +214,38 @@ inline int attn_rc_grid(int nwin) {
   const int gx = bwd_persistent_grid(nwin, 12 / 4, 4);
   return gx >= 8 ? gx / 8 * 8 : 8;
 }
+
+// ================================================================================= shifted window attention on a zero-padded grid
+// (attention_sp.hip: sodt_window_attn_sp_fwd / _bwd).  8x8 windows over the padded grid Hp x Wp of an H x W token grid that is
+// no multiple of 8; the padded grid exists as index arithmetic only.
+namespace {   // unnamed for the reason AttnGeo is
+struct SpGeo {
+  int B, H, W, C, heads, shift;
+  int nwy, nwx;           // windows per column / row of the PADDED grid
+};
+}  // namespace
+
+inline bool make_sp_geo(SpGeo& g, int B, int H, int W, int C, int heads, int ws, int shift) {
+  if (B <= 0 || heads <= 0 || C <= 0 || (C % heads)) return false;
+  if (ws != 8 || shift <= 0 || shift >= ws || H <= ws || W <= ws) return false;
+  if ((H % ws) == 0 && (W % ws) == 0) return false;            // an unpadded grid is sodt_window_attn_fwd's
+  g.B = B; g.H = H; g.W = W; g.C = C; g.heads = heads; g.shift = shift;
+  g.nwy = (H + ws - 1) / ws; g.nwx = (W + ws - 1) / ws;
+  return (long)B * g.nwy * g.nwx * 64 * heads < (1L << 31);    // token rows and the forward's grid (windows x head groups) are int
+}
+
+// one wave per (window, head), nw heads per workgroup; head dim 16 or 32 only.  nw == 0: refused (SODT_EINVAL)
+inline int attn_sp_fwd_route(int dtype, int hd, const SpGeo& g) {
+  const int nw = (hd == 16 || hd == 32) ? attn_nw(dtype, hd, false) : 0;
+  return (nw && g.heads % nw == 0) ? nw : 0;
+}
+inline int attn_sp_bwd_route(int dtype, int hd, const SpGeo& g) {
+  const int nw = (hd == 16 || hd == 32) ? attn_nw(dtype, hd, true) : 0;
+  return (nw && g.heads % nw == 0) ? nw : 0;
+}
+// persistent grid of the backward: the workgroups resident at once (its LDS footprint allows one per CU)
+inline int attn_sp_bwd_grid(int nwin, int ngroups) {
+  int gx = 256 / (ngroups > 0 ? ngroups : 1);
+  if (gx < 1) gx = 1;
+  return nwin < gx ? nwin : gx;
+}

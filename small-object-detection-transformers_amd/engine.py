@@ -95,6 +95,7 @@ class Plan:
 
 # what _block_route chooses among (BlockRoute.attn / .mlp)
 ATTN_FUSED_RC, ATTN_FUSED_SAVED, ATTN_PADDED, ATTN_PLAIN = "fused, q/k/v recomputed", "fused, q/k/v saved", "padded", "plain"
+ATTN_SHIFT_PAD = "shifted, padded"      # only with Engine.pad_shifted_blocks (Model.pad_shifted_blocks)
 MLP_FUSED, MLP_LIN_RC, MLP_LIN_SAVED, MLP_FOLD, MLP_CONV = "fused linear", "linear, activation saved", "linear, pre-activation saved", \
     "folded conv", "three-GEMM conv"
 
@@ -217,6 +218,9 @@ class Engine:
         # anchor that makes the autograd node require grad even if the caller froze everything else
         self._anchor = torch.zeros(1, device=self.dev, requires_grad=True)
         self.ddp = None     # set by ddp.attach()
+        # Shifted blocks on a grid that is no multiple of their window (S % 64 == 32: stage 2) run csrc/attention_sp.hip instead of
+        # being refused.  Opt-in; run() copies Model.pad_shifted_blocks here and drops the cached plans when it changes.
+        self.pad_shifted_blocks = False
         self.use_fused_wmsa = True     # tests / tools may switch the fused block kernel off to compare with the four launches it replaces
         self.use_fused_mlp = True      # the same for the fused linear MLP (csrc/mlp.hip) against its two GEMM launches
         # bf16, C = 192: backward of attn.proj and of the conv-MLP's fc2 as ONE launch each (csrc/linbwd.hip: dX and dW from one read
@@ -439,6 +443,10 @@ class Engine:
                              "the kernels take raw device pointers")
         x_rgb = x_rgb.float().contiguous()
         x_ir = x_ir.float().contiguous()
+        psb = bool(getattr(self.model, "pad_shifted_blocks", False))
+        if psb != self.pad_shifted_blocks:
+            self.pad_shifted_blocks = psb
+            self.plans.clear()                                   # recorded launch lists hold the routes of the other setting
         key = (B, S, dt, training)
         plan = self.plans.pop(key, None)
         if plan is None:
@@ -637,10 +645,12 @@ class Engine:
         # (backbone_vit.py:619-672, window_partition / window_unpartition), so a pad token enters the attention as the qkv BIAS.
         # Unshifted blocks (stage 3 at S = 640, 768, ...: 40 x 40, 48 x 48 tokens against the 32-token window) run through the
         # spatial K-segments: the QKV GEMM writes the padded grid (rows outside read zeros), the attention runs on it, the
-        # projection reads it back cropped.  Shifted blocks would also need the reference's mask of the UNPADDED grid: not built.
+        # projection reads it back cropped.  Shifted blocks also need the reference's roll and mask of the UNPADDED grid: with
+        # pad_shifted_blocks they run on the unpadded tensors, the padded grid being index arithmetic inside
+        # sodt_window_attn_sp_fwd / _bwd (8-token windows: stage 2 at S % 64 == 32); without the switch they are refused.
         Hp, Wp = H + (-H) % ws, W + (-W) % ws
         pad = (Hp, Wp) if (Hp, Wp) != (H, W) else None
-        if pad and shift > 0:
+        if pad and shift > 0 and not (self.pad_shifted_blocks and ws == 8):
             raise NotImplementedError(f"{tag}: {H}x{W} tokens are not a multiple of the {ws}-token window of a SHIFTED block (the "
                                       "reference's zero padding, backbone_vit.py:619-643, is built for unshifted blocks only): choose "
                                       "an input size S that is a multiple of 64")
@@ -650,7 +660,7 @@ class Engine:
             # recomputes them from xn1 and the parameter pack (sodt_wmsa_block_bwd): 604 MB less written per launch
             attn = ATTN_FUSED_SAVED if plan.dt == torch.float32 else ATTN_FUSED_RC
         else:
-            attn = ATTN_PADDED if pad else ATTN_PLAIN
+            attn = (ATTN_SHIFT_PAD if shift > 0 else ATTN_PADDED) if pad else ATTN_PLAIN
         if blk.mlp.linear:
             # Linear MLPs on the bf16 path keep only GELU(h): the backward recomputes h inside the dh GEMM
             rc = ops.mlp_recompute_ok(M, Cc, plan.dt) and (pre + "mlp.fc1.weight") in P["wcat"]
@@ -705,6 +715,14 @@ class Engine:
             ops.window_attn_fwd(qkv, bias_t, aop, lse, B, Hp, Wp, Cc, HEADS, ws, 0)
             ops.gemm_nt([SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, spatial=(H, W),
                         bias=p[pre + "attn.proj.bias"], resid=x_in)
+        elif r.attn == ATTN_SHIFT_PAD:
+            # every tensor on the unpadded grid: a pad key reads qkv.bias inside the kernel, a pad query is never computed
+            ao = plan.buf(tag + ".ao", (M, Cc))
+            qkv = plan.buf(tag + ".qkv", (M, 3 * Cc))
+            ops.gemm_nt([SegSpec(xn1)], w[pre + "attn.qkv.weight"], qkv, M, 3 * Cc, Cc, bias=p[pre + "attn.qkv.bias"])
+            lse = plan.buf(tag + ".lse", (M, HEADS), torch.float32)
+            ops.window_attn_sp_fwd(qkv, p[pre + "attn.qkv.bias"], bias_t, ao, lse, B, H, W, Cc, HEADS, ws, shift)
+            ops.gemm_nt([SegSpec(ao)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, bias=p[pre + "attn.proj.bias"], resid=x_in)
         else:
             ao = plan.buf(tag + ".ao", (M, Cc))
             qkv = plan.buf(tag + ".qkv", (M, 3 * Cc))
@@ -865,6 +883,11 @@ class Engine:
                 ops.wmsa_block_bwd(xn1, r.wpk, bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
             elif r.attn == ATTN_FUSED_SAVED:
                 ops.window_attn_bwd_wm(b[tag + ".qkvw"], bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
+            elif r.attn == ATTN_SHIFT_PAD:
+                # the pad keys' k / v gradient belongs to qkv.bias (their k / v ARE the bias): added there by the kernel, beside the
+                # column sums of dqkv the linear backward below adds
+                ops.window_attn_sp_bwd(b[tag + ".qkv"], p[pre + "attn.qkv.bias"], bias_t, ao, dao, b[tag + ".lse"], dqkv,
+                                       g[pre + "attn.qkv.bias"], dbt, B, H, W, Cc, HEADS, ws, shift)
             else:
                 scratch = plan.scratch("attn_scratch", (M * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
                 ops.window_attn_bwd(b[tag + ".qkv"], bias_t, ao, dao, b[tag + ".lse"], dqkv, dbt, scratch, B, H, W, Cc, HEADS, ws, shift)

@@ -374,6 +374,9 @@ class Model(nn.Module):
                 mod.momentum = 0.03
         self.compute_dtype: Optional[torch.dtype] = None        # None: bf16 under autocast, else f32
         self.materialize_features = False
+        # True: shifted blocks whose grid is no multiple of their 8-token window run on the reference's zero padding
+        # (csrc/attention_sp.hip) instead of being refused - every multiple of 32 from 576 runs, and 544.  Read at each forward.
+        self.pad_shifted_blocks = False
         self._engine = None
         self._nms: Optional[NMS] = None      # set by .nms(); kept outside self.model so state_dict keys do not move
 
@@ -440,7 +443,9 @@ class Model(nn.Module):
         ``Engine._block_route`` refuse (tests/test_multiscale_gpu.py holds the two together): S is a multiple of 32; a stage
         no larger than its window is ONE window, of side 8, 16 or 32 (the attention kernels walk 64-token tiles of whole window
         rows); the window matches the block's relative-position bias table; and a stage that is not a multiple of its window
-        is zero-padded for unshifted blocks only.  For a model built at 512 or 1024: S = 512 and every multiple of 64 from 576."""
+        is zero-padded for unshifted blocks only - or, with ``pad_shifted_blocks`` set, for shifted blocks of 8-token windows too.
+        For a model built at 512 or 1024: S = 512 and every multiple of 64 from 576; with the switch on 512, 544 and every
+        multiple of 32 from 576."""
         if isinstance(S, bool) or not isinstance(S, int) or S <= 0 or S % 32:
             return False
         enc = self.image_encoder
@@ -453,7 +458,7 @@ class Model(nn.Module):
                         return False
                 if blk.attn.relative_position_bias_table.shape[0] != (2 * ws - 1) ** 2:
                     return False
-                if H % ws and shift > 0:
+                if H % ws and shift > 0 and not (getattr(self, "pad_shifted_blocks", False) and ws == 8):
                     return False
         return True
 

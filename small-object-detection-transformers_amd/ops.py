@@ -363,6 +363,16 @@ def wmsa_block_fwd(x, wpk, xm, xn2, st1, st2, xn1, qkvw, lsew, ao, B, H, W, Cc, 
             B, H, W, Cc, heads, ws, shift, dt_code(x))
 
 
+def window_attn_sp_fwd(qkv, qkv_bias, bias_t, out, lse, B, H, W, Cc, heads, ws, shift):
+    """shifted block on a zero-padded grid (csrc/attention_sp.hip): operands on the unpadded grid, a pad key reads qkv_bias"""
+    _launch("sodt_window_attn_sp_fwd", _p(qkv), _p(qkv_bias), _p(bias_t), _p(out), _p(lse), B, H, W, Cc, heads, ws, shift, dt_code(qkv))
+
+
+def window_attn_sp_bwd(qkv, qkv_bias, bias_t, out, dout, lse, dqkv, dqkv_bias, dbias_t, B, H, W, Cc, heads, ws, shift):
+    _launch("sodt_window_attn_sp_bwd", _p(qkv), _p(qkv_bias), _p(bias_t), _p(out), _p(dout), _p(lse), _p(dqkv), _p(dqkv_bias),
+            _p(dbias_t), B, H, W, Cc, heads, ws, shift, dt_code(qkv))
+
+
 def window_attn_bwd_wm(qkvw, bias_t, dout, lsew, dqkv, dbias_t, B, H, W, Cc, heads, ws, shift):
     _launch("sodt_window_attn_bwd_wm", _p(qkvw), _p(bias_t), _p(dout), _p(lsew), _p(dqkv), _p(dbias_t),
             B, H, W, Cc, heads, ws, shift, dt_code(dout))
