@@ -392,6 +392,8 @@ int sodt_bn_finalize(const double* stats, float* mean_rstd, float* running_mean,
 /* scale = gamma*rstd, shift = beta - mean*scale: the fused / eval-mode form (torch_utils.py:182-203) */
 int sodt_bn_affine(const float* mean_rstd, const float* gamma, const float* beta, float* scale, float* shift,
                    int C, sodt_stream_t st);
+/* The three BatchNorm+SiLU launches take rows of at most 256 16-byte chunks (C <= 2048 in bf16, 1024 in f32): a thread keeps one
+   chunk of the row for the whole launch.  Wider rows return SODT_EINVAL. */
 int sodt_bn_silu_fwd(const void* z, const float* mean_rstd, const float* gamma, const float* beta,
                      void* y, int ldy, long M, int C, int dtype, sodt_stream_t st);
 /* pass 1: red[0][c] += sum g, red[1][c] += sum g*xhat with g = dy * silu'(a);  pass 2: dz */

@@ -41,24 +41,54 @@ __global__ void bn_affine_kernel(const float* __restrict__ mr, const float* __re
   shift[c] = beta[c] - mr[c] * s;
 }
 
+// The three BatchNorm+SiLU kernels below walk the rows the same way: C / KPL threads cover one row in 16-byte chunks, a workgroup
+// covers rpp = 256 / (C / KPL) rows per pass, and the grid stride is a whole number of passes, so a thread keeps its channel group for
+// the whole launch and holds that group's parameters in registers.  A trip is several passes whose 16-byte loads are all issued
+// before the first is used: with one row per trip a thread has 16 or 32 bytes in flight and the launch runs at half the HBM rate
+// (2.6 TB/s at 512 K rows x 64 channels).
+#ifndef BN_FWD_ROWS
+#define BN_FWD_ROWS 2
+#define BN_FWD_GRID 4096
+#define BN_RED_ROWS 8
+#define BN_RED_GRID 256
+#define BN_APP_ROWS 4
+#define BN_APP_GRID 512
+#endif
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_silu_fwd_kernel(const T* __restrict__ z, const float* __restrict__ mr,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          T* __restrict__ y, int ldy, long M, int C) {
   constexpr int KPL = TT<T>::KPL;
+  constexpr int U = BN_FWD_ROWS;
   const int CH = C / KPL;
-  const long total = M * CH;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long m = i / CH; const int c0 = (int)(i - m * CH) * KPL;
-    float v[KPL];
-    unpack<T>(*(const uint4*)(z + m * C + c0), v);
+  const int rpp = 256 / CH;                  // rows per pass
+  const int rl = threadIdx.x / CH, ch = threadIdx.x - rl * CH;
+  if (rl >= rpp) return;
+  const int c0 = ch * KPL;
+  float mu[KPL], rs[KPL], ga[KPL], be[KPL];
 #pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-      const int c = c0 + j;
-      const float a = (v[j] - mr[c]) * mr[C + c] * gamma[c] + beta[c];
-      v[j] = a * sigmoid_f(a);
+  for (int j = 0; j < KPL; ++j) { mu[j] = mr[c0 + j]; rs[j] = mr[C + c0 + j]; ga[j] = gamma[c0 + j]; be[j] = beta[c0 + j]; }
+  const long stride = (long)gridDim.x * rpp;
+  for (long m = (long)blockIdx.x * rpp + rl; m < M; m += U * stride) {
+    uint4 vq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long mm = m + u * stride;
+      vq[u] = mm < M ? *(const uint4*)(z + mm * C + c0) : make_uint4(0u, 0u, 0u, 0u);
     }
-    *(uint4*)(y + m * ldy + c0) = pack<T>(v);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long mm = m + u * stride;
+      float v[KPL];
+      unpack<T>(vq[u], v);
+#pragma unroll
+      for (int j = 0; j < KPL; ++j) {
+        const float a = __builtin_fmaf((v[j] - mu[j]) * rs[j], ga[j], be[j]);
+        v[j] = a * sigmoid_f(a);
+      }
+      if (mm < M) *(uint4*)(y + mm * ldy + c0) = pack<T>(v);
+    }
   }
 }
 
@@ -109,12 +139,15 @@ __global__ __launch_bounds__(256) void col_stats_kernel(const T* __restrict__ z,
 }
 
 // per-channel  red[0][c] += sum_m g,  red[1][c] += sum_m g * xhat,   g = dy * silu'(a)
+// Every workgroup ends with 2 C f64 atomics on the same 2 C words, which execute one after the other at the memory side: the grid
+// is sized so that a workgroup walks several trips before it pays them (sodt_bn_silu_bwd_reduce).
 template <typename T>
 __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z,
                                                                 const float* __restrict__ mr, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, double* __restrict__ red,
                                                                 long M, int C) {
   constexpr int KPL = TT<T>::KPL;
+  constexpr int U = BN_RED_ROWS;
   __shared__ float sred[2][256 * KPL];
   const int CH = C / KPL;
   const int rpp = 256 / CH;                  // rows per pass
@@ -129,20 +162,18 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const T* __rest
     mu[j] = mr[c]; rs[j] = mr[C + c]; ga[j] = gamma[c]; be[j] = beta[c]; a0[j] = 0.f; a1[j] = 0.f;
   }
   if (act) {
-    // four rows per trip, their eight 16-byte loads issued before the first is used: with one row per trip a thread has 32 bytes in
-    // flight and the launch runs at half the HBM rate (2.6 TB/s at 512 K rows x 64 channels)
     const long stride = (long)gridDim.x * rpp;
-    for (long m = (long)blockIdx.x * rpp + rl; m < M; m += 4 * stride) {
-      uint4 dq[4], vq[4];
+    for (long m = (long)blockIdx.x * rpp + rl; m < M; m += U * stride) {
+      uint4 dq[U], vq[U];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < U; ++u) {
         const long mm = m + u * stride;
         const bool ok = mm < M;
         dq[u] = ok ? *(const uint4*)(dy + mm * lddy + c0) : make_uint4(0u, 0u, 0u, 0u);
         vq[u] = ok ? *(const uint4*)(z + mm * C + c0) : make_uint4(0u, 0u, 0u, 0u);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < U; ++u) {
         float d[KPL], v[KPL];
         unpack<T>(dq[u], d);
         unpack<T>(vq[u], v);
@@ -169,6 +200,27 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const T* __rest
   }
 }
 
+// One element of dz = gamma rstd (g - mean_m g - xhat mean_m (g xhat)),  g = dy silu'(a).  Under -ffp-contract=fast the backend fuses
+// every multiply-add that the vectoriser has left scalar, so which roundings happen would follow from how a loop was unrolled;
+// here each one is written out instead: __builtin_fmaf where a product is fused into the sum after it, hold() (opaque to the
+// optimiser) where it is rounded first.  The bf16 and f32 forms differ in two places; both are what these kernels have always
+// returned, bit for bit.
+__device__ __forceinline__ float hold(float v) { asm("" : "+v"(v)); return v; }
+
+template <typename T>
+__device__ __forceinline__ float bn_dz(float d, float xh, float a, float gars, float mg, float mgx) {
+  const float sg = sigmoid_f(a);
+  if constexpr (TT<T>::KPL == 8) {
+    const float t = 1.0f + hold(a * (1.0f - sg));
+    return gars * (__builtin_fmaf(d * sg, t, -mg) - hold(xh * mgx));
+  } else {
+    const float t = __builtin_fmaf(a, 1.0f - sg, 1.0f);
+    return gars * __builtin_fmaf(-xh, mgx, __builtin_fmaf(d * sg, t, -mg));
+  }
+}
+
+// dz = gamma rstd (g - mean_m g - xhat mean_m (g xhat)) from the finished sums; workgroup 0 also adds them to dgamma / dbeta.
+// The two means are one f64 product rounded once to f32, formed once per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z,
                                                                const float* __restrict__ mr, const float* __restrict__ gamma,
@@ -176,29 +228,46 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restr
                                                                T* __restrict__ dz, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta, long M, int C) {
   constexpr int KPL = TT<T>::KPL;
+  constexpr int U = BN_APP_ROWS;
   const int CH = C / KPL;
-  const long total = M * CH;
+  const int rpp = 256 / CH;                  // rows per pass
   const double invM = 1.0 / (double)M;
   if (blockIdx.x == 0) {
     for (int c = threadIdx.x; c < C; c += 256) { dbeta[c] += (float)red[c]; dgamma[c] += (float)red[C + c]; }
   }
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long m = i / CH; const int c0 = (int)(i - m * CH) * KPL;
-    float d[KPL], v[KPL], o[KPL];
-    unpack<T>(*(const uint4*)(dy + m * lddy + c0), d);
-    unpack<T>(*(const uint4*)(z + m * C + c0), v);
+  const int rl = threadIdx.x / CH, ch = threadIdx.x - rl * CH;
+  if (rl >= rpp) return;
+  const int c0 = ch * KPL;
+  float mu[KPL], rs[KPL], ga[KPL], be[KPL], gr[KPL], mg[KPL], mgx[KPL];
 #pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-      const int c = c0 + j;
-      const float rs = mr[C + c], ga = gamma[c];
-      const float xh = (v[j] - mr[c]) * rs;
-      const float a = xh * ga + beta[c];
-      const float sg = sigmoid_f(a);
-      const float gg = d[j] * sg * (1.0f + a * (1.0f - sg));
-      const float mg = (float)(red[c] * invM), mgx = (float)(red[C + c] * invM);
-      o[j] = ga * rs * (gg - mg - xh * mgx);
+  for (int j = 0; j < KPL; ++j) {
+    const int c = c0 + j;
+    mu[j] = mr[c]; rs[j] = mr[C + c]; ga[j] = gamma[c]; be[j] = beta[c]; gr[j] = ga[j] * rs[j];
+    mg[j] = (float)(red[c] * invM); mgx[j] = (float)(red[C + c] * invM);
+  }
+  const long stride = (long)gridDim.x * rpp;
+  for (long m = (long)blockIdx.x * rpp + rl; m < M; m += U * stride) {
+    uint4 dq[U], vq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long mm = m + u * stride;
+      const bool ok = mm < M;
+      dq[u] = ok ? *(const uint4*)(dy + mm * lddy + c0) : make_uint4(0u, 0u, 0u, 0u);
+      vq[u] = ok ? *(const uint4*)(z + mm * C + c0) : make_uint4(0u, 0u, 0u, 0u);
     }
-    *(uint4*)(dz + m * C + c0) = pack<T>(o);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long mm = m + u * stride;
+      float d[KPL], v[KPL], o[KPL];
+      unpack<T>(dq[u], d);
+      unpack<T>(vq[u], v);
+#pragma unroll
+      for (int j = 0; j < KPL; ++j) {
+        const float xh = (v[j] - mu[j]) * rs[j];
+        o[j] = bn_dz<T>(d[j], xh, __builtin_fmaf(xh, ga[j], be[j]), gr[j], mg[j], mgx[j]);
+      }
+      if (mm < M) *(uint4*)(dz + mm * C + c0) = pack<T>(o);
+    }
   }
 }
 
@@ -376,6 +445,13 @@ inline unsigned nblocks(long work, int cap = 4096) {
   return (unsigned)b;
 }
 
+// grid of the BatchNorm+SiLU kernels: one workgroup per trip (`rows` passes of 256 / ch rows), at most `cap` of them
+inline unsigned bn_grid(long M, int ch, int rows, int cap) {
+  const long per = (long)rows * (256 / ch);
+  const long g = (M + per - 1) / per;
+  return (unsigned)(g > cap ? cap : g);
+}
+
 }  // namespace
 
 extern "C" int sodt_bn_finalize(const double* stats, float* mean_rstd, float* running_mean, float* running_var,
@@ -394,8 +470,8 @@ extern "C" int sodt_bn_affine(const float* mean_rstd, const float* gamma, const 
 extern "C" int sodt_bn_silu_fwd(const void* z, const float* mean_rstd, const float* gamma, const float* beta,
                                 void* y, int ldy, long M, int C, int dtype, sodt_stream_t st) {
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
-  if (!z || !y || M <= 0 || C <= 0 || (C % kpl) || (ldy % kpl)) return SODT_EINVAL;
-  const unsigned gr = nblocks(M * (C / kpl));
+  if (!z || !y || M <= 0 || C <= 0 || (C % kpl) || (ldy % kpl) || C / kpl > 256) return SODT_EINVAL;
+  const unsigned gr = bn_grid(M, C / kpl, BN_FWD_ROWS, BN_FWD_GRID);
   if (dtype == SODT_BF16) return sodt_launch<bn_silu_fwd_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)z, mean_rstd, gamma, beta, (bf16*)y, ldy, M, C);
   if (dtype == SODT_F32) return sodt_launch<bn_silu_fwd_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)z, mean_rstd, gamma, beta, (float*)y, ldy, M, C);
   return SODT_EINVAL;
@@ -406,10 +482,9 @@ extern "C" int sodt_bn_silu_bwd_reduce(const void* dy, int lddy, const void* z, 
                                        int dtype, sodt_stream_t st) {
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!dy || !z || !red || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
-  const int rpp = 256 / (C / kpl);
-  long gr = (M + rpp - 1) / rpp; if (gr > 1024) gr = 1024;
-  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_reduce_kernel<bf16>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, M, C);
-  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_reduce_kernel<float>>(dim3((unsigned)gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, M, C);
+  const unsigned gr = bn_grid(M, C / kpl, BN_RED_ROWS, BN_RED_GRID);
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_reduce_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, M, C);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_reduce_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, M, C);
   return SODT_EINVAL;
 }
 
@@ -427,8 +502,8 @@ extern "C" int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, c
                                       const float* gamma, const float* beta, const double* red, void* dz,
                                       float* dgamma, float* dbeta, long M, int C, int dtype, sodt_stream_t st) {
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
-  if (!dy || !z || !red || !dz || !dgamma || !dbeta || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl)) return SODT_EINVAL;
-  const unsigned gr = nblocks(M * (C / kpl));
+  if (!dy || !z || !red || !dz || !dgamma || !dbeta || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
+  const unsigned gr = bn_grid(M, C / kpl, BN_APP_ROWS, BN_APP_GRID);
   if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C);
   if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C);
   return SODT_EINVAL;

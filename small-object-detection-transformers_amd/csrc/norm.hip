@@ -53,6 +53,16 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
   }
 }
 
+// Rows per wave per trip and the grid cap of ln_bwd_kernel for rows of more than 64 chunks.  Every workgroup ends with 2 C f32
+// atomics on the same 2 C words, which execute one after the other at the memory side: at C = 768 a grid of 1024 workgroups spent
+// more time there than on its rows.  So the grid is small, and a wave keeps LN_BWD_ROWS rows in flight (all their 16-byte loads
+// issued before the first is used) instead.  Rows of at most 64 chunks (C = 384 in bf16 is 48) run at rate with one row per trip on
+// the full grid and lost with every smaller one (profiles/r10_norm_ab.md), so they keep it.
+#ifndef LN_BWD_ROWS
+#define LN_BWD_ROWS 2
+#define LN_BWD_GRID 512
+#endif
+
 template <typename T, int MAXCH>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const float* __restrict__ stats, const float* __restrict__ gamma,
@@ -60,6 +70,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
                                                      float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                      int M, int C) {
   constexpr int KPL = TT<T>::KPL;
+  constexpr int R = MAXCH >= 2 ? LN_BWD_ROWS : 1;
   __shared__ float red[4][64 * MAXCH * KPL + 1];   // per-wave partials of one parameter vector at a time
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nch = C / KPL;
@@ -74,41 +85,104 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
       gm[i][j] = (ch < nch) ? gamma[ch * KPL + j] : 0.f;
     }
   }
-  for (long row = (long)blockIdx.x * 4 + wid; row < M; row += (long)gridDim.x * 4) {
-    const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
-    float xh[MAXCH][KPL], g[MAXCH][KPL];
-    float c1 = 0.f, c2 = 0.f;
+  if constexpr (R == 1) {   // one row per wave per trip, loaded where it is used
+    for (long row = (long)blockIdx.x * 4 + wid; row < M; row += (long)gridDim.x * 4) {
+      const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
+      float xh[MAXCH][KPL], g[MAXCH][KPL];
+      float c1 = 0.f, c2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      const int ch = lane + 64 * i;
-      if (ch < nch) {
-        float a[KPL], d[KPL];
-        unpack<T>(*(const uint4*)(x + row * C + ch * KPL), a);
-        unpack<T>(*(const uint4*)(dy + row * C + ch * KPL), d);
+      for (int i = 0; i < MAXCH; ++i) {
+        const int ch = lane + 64 * i;
+        if (ch < nch) {
+          float a[KPL], d[KPL];
+          unpack<T>(*(const uint4*)(x + row * C + ch * KPL), a);
+          unpack<T>(*(const uint4*)(dy + row * C + ch * KPL), d);
 #pragma unroll
-        for (int j = 0; j < KPL; ++j) {
-          xh[i][j] = (a[j] - mean) * rstd;
-          g[i][j] = d[j] * gm[i][j];
-          c1 += g[i][j]; c2 += g[i][j] * xh[i][j];
-          ag[i][j] += d[j] * xh[i][j]; ab[i][j] += d[j];
+          for (int j = 0; j < KPL; ++j) {
+            xh[i][j] = (a[j] - mean) * rstd;
+            g[i][j] = d[j] * gm[i][j];
+            c1 += g[i][j]; c2 += g[i][j] * xh[i][j];
+            ag[i][j] += d[j] * xh[i][j]; ab[i][j] += d[j];
+          }
+        }
+      }
+      c1 = wave_sum(c1) * invC; c2 = wave_sum(c2) * invC;
+#pragma unroll
+      for (int i = 0; i < MAXCH; ++i) {
+        const int ch = lane + 64 * i;
+        if (ch < nch) {
+          float o[KPL];
+#pragma unroll
+          for (int j = 0; j < KPL; ++j) o[j] = rstd * (g[i][j] - c1 - xh[i][j] * c2);
+          if (dres) {
+            float r[KPL];
+            unpack<T>(*(const uint4*)(dres + row * C + ch * KPL), r);
+#pragma unroll
+            for (int j = 0; j < KPL; ++j) o[j] += r[j];
+          }
+          *(uint4*)(dx + row * C + ch * KPL) = pack<T>(o);
         }
       }
     }
-    c1 = wave_sum(c1) * invC; c2 = wave_sum(c2) * invC;
+  } else {                    // R rows per wave per trip, all their loads issued first
+    for (long row0 = ((long)blockIdx.x * 4 + wid) * R; row0 < M; row0 += (long)gridDim.x * 4 * R) {
+      uint4 xq[R][MAXCH], dq[R][MAXCH], rq[R][MAXCH];
+      float mean[R], rstd[R];
 #pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      const int ch = lane + 64 * i;
-      if (ch < nch) {
-        float o[KPL];
+      for (int r = 0; r < R; ++r) {
+        const long row = row0 + r;
+        if (row < M) {                                // (the same for every lane of the wave)
+          mean[r] = stats[row * 2]; rstd[r] = stats[row * 2 + 1];
 #pragma unroll
-        for (int j = 0; j < KPL; ++j) o[j] = rstd * (g[i][j] - c1 - xh[i][j] * c2);
-        if (dres) {
-          float r[KPL];
-          unpack<T>(*(const uint4*)(dres + row * C + ch * KPL), r);
-#pragma unroll
-          for (int j = 0; j < KPL; ++j) o[j] += r[j];
+          for (int i = 0; i < MAXCH; ++i) {
+            const int ch = lane + 64 * i;
+            if (ch < nch) {
+              xq[r][i] = *(const uint4*)(x + row * C + ch * KPL);
+              dq[r][i] = *(const uint4*)(dy + row * C + ch * KPL);
+              if (dres) rq[r][i] = *(const uint4*)(dres + row * C + ch * KPL);
+            }
+          }
         }
-        *(uint4*)(dx + row * C + ch * KPL) = pack<T>(o);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const long row = row0 + r;
+        if (row >= M) break;
+        float xh[MAXCH][KPL], g[MAXCH][KPL];
+        float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i) {
+          const int ch = lane + 64 * i;
+          if (ch < nch) {
+            float a[KPL], d[KPL];
+            unpack<T>(xq[r][i], a);
+            unpack<T>(dq[r][i], d);
+#pragma unroll
+            for (int j = 0; j < KPL; ++j) {
+              xh[i][j] = (a[j] - mean[r]) * rstd[r];
+              g[i][j] = d[j] * gm[i][j];
+              c1 += g[i][j]; c2 += g[i][j] * xh[i][j];
+              ag[i][j] += d[j] * xh[i][j]; ab[i][j] += d[j];
+            }
+          }
+        }
+        c1 = wave_sum(c1) * invC; c2 = wave_sum(c2) * invC;
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i) {
+          const int ch = lane + 64 * i;
+          if (ch < nch) {
+            float o[KPL];
+#pragma unroll
+            for (int j = 0; j < KPL; ++j) o[j] = rstd[r] * (g[i][j] - c1 - xh[i][j] * c2);
+            if (dres) {
+              float q[KPL];
+              unpack<T>(rq[r][i], q);
+#pragma unroll
+              for (int j = 0; j < KPL; ++j) o[j] += q[j];
+            }
+            *(uint4*)(dx + row * C + ch * KPL) = pack<T>(o);
+          }
+        }
       }
     }
   }
@@ -261,15 +335,16 @@ extern "C" int sodt_layernorm_bwd(const void* dy, const void* x, const float* st
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (M <= 0 || C <= 0 || (C % kpl) || C > 256 * kpl || !x || !dy || !dx || !stats || !gamma || !dgamma || !dbeta)
     return SODT_EINVAL;
-  long blocks = ((long)M + 3) / 4;
-  if (blocks > 1024) blocks = 1024;
+  const int nc = (C / kpl + 63) / 64;
+  const int rows = nc >= 2 ? LN_BWD_ROWS : 1, cap = nc >= 2 ? LN_BWD_GRID : 1024;     // (ln_bwd_kernel's R)
+  long blocks = ((long)M + 4 * rows - 1) / (4 * rows);
+  if (blocks > cap) blocks = cap;
   if (C / kpl <= 32) {
     long hb = ((long)M + 7) / 8;
     if (hb > 1024) hb = 1024;
     if (dtype == SODT_BF16) return sodt_launch<ln_bwd_half_kernel<bf16>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, (const bf16*)x, stats, gamma, (const bf16*)dres, (bf16*)dx, dgamma, dbeta, M, C);
     return sodt_launch<ln_bwd_half_kernel<float>>(dim3((unsigned)hb), dim3(256), 0, (hipStream_t)st, (const float*)dy, (const float*)x, stats, gamma, (const float*)dres, (float*)dx, dgamma, dbeta, M, C);
   }
-  const int nc = (C / kpl + 63) / 64;
 #define LNB(TY, NC) sodt_launch<ln_bwd_kernel<TY, NC>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
                        (const TY*)dy, (const TY*)x, stats, gamma, (const TY*)dres, (TY*)dx, dgamma, dbeta, M, C)
   if (dtype == SODT_BF16) return nc == 1 ? LNB(bf16, 1) : nc == 2 ? LNB(bf16, 2) : LNB(bf16, 4);

@@ -94,6 +94,17 @@ def cost(name, args):
     if name == "sodt_col_stats":
         M, C = val(args[3]), val(args[4])
         return (f"M={M} C={C}", M * C * ES, 0.0)
+    # BatchNorm+SiLU of the head's Conv units: z in, y out / dy, z in / dy, z in, dz out, plus the per-channel vectors
+    # (mean, rstd, gamma, beta in f32; the two f64 sums)
+    if name == "sodt_bn_silu_fwd":
+        M, C = val(args[6]), val(args[7])
+        return (f"M={M} C={C}", 2.0 * M * C * ES + 16 * C, 0.0)
+    if name == "sodt_bn_silu_bwd_reduce":
+        M, C = val(args[7]), val(args[8])
+        return (f"M={M} C={C}", 2.0 * M * C * ES + 32 * C, 0.0)
+    if name == "sodt_bn_silu_bwd_apply":
+        M, C = val(args[10]), val(args[11])
+        return (f"M={M} C={C}", 3.0 * M * C * ES + 40 * C, 0.0)
     if name == "sodt_layernorm_fwd":
         M, C = val(args[5]), val(args[6])
         return (f"M={M} C={C}", M * (2 * C * ES + 8), 0.0)
