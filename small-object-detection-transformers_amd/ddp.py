@@ -14,6 +14,11 @@ asynchronously while the backward of the earlier layers keeps the GPU busy
 slice follows the last weight gradient (``finish``).  88 MB are ~1 ms ring-bound on
 7 x 153 GB/s links against ~30 ms of backward.
 
+Frozen parameters (``requires_grad = False``, Train.py:115-121): the buffer's head is the
+forward's beginning, so a frozen forward prefix is a run of zeros at the front of the buffer
+on every rank.  The engine hands ``reduce`` / ``reduce_async`` / ``finish`` only
+``flat_grad[first_trainable_offset:]`` (freeze.py), and only the buckets whose backward ran.
+
 Gradient accumulation (Train.py:125,448: nbs 64 / batch 16 -> 4 micro-steps per optimizer
 step): the weight-gradient kernels accumulate (``+=``) into the flat buffer, so a second
 all-reduce of a buffer that already holds reduced values would count them ``world`` times.
@@ -69,9 +74,10 @@ class GradReducer:
     def reduce(self, flat_grad: torch.Tensor) -> None:
         if not self._active():
             return
-        dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
-        if self.average:
-            flat_grad.mul_(1.0 / self.world)
+        if flat_grad.numel():
+            dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
+            if self.average:
+                flat_grad.mul_(1.0 / self.world)
         self._dirty = True
 
     def reduce_async(self, part: torch.Tensor) -> None:
@@ -86,9 +92,10 @@ class GradReducer:
         """All-reduce the remaining slice, then make the current stream wait for the asynchronous ones."""
         if not self._active():
             return
-        dist.all_reduce(rest, op=dist.ReduceOp.SUM, group=self.group)
-        if self.average:
-            rest.mul_(1.0 / self.world)
+        if rest.numel():                    # (empty: everything below the asynchronous buckets is frozen)
+            dist.all_reduce(rest, op=dist.ReduceOp.SUM, group=self.group)
+            if self.average:
+                rest.mul_(1.0 / self.world)
         for work, part in self._pending:
             work.wait()
             if self.average:

@@ -1,8 +1,10 @@
 """Execution engine: the whole forward AND backward of Model(model.yaml) as a fixed
 sequence of HIP kernels (C ABI, include/sodt_hip.h), token-major activations.
 
-* One ``Plan`` per (batch, resolution, dtype, mode): every activation / gradient buffer
-  is allocated once; the first run records every launch, later runs replay the list.
+* One ``Plan`` per (batch, resolution, dtype, mode) - and, in training mode, per set of
+  ``requires_grad`` flags (freeze.py: frozen units have no backward launch and save nothing):
+  every activation / gradient buffer is allocated once; the first run records every launch,
+  later runs replay the list.
 * Backward is hand-written (no torch autograd inside): ``_EngineFn`` is a single
   autograd node whose backward runs the recorded reverse sequence and deposits parameter
   gradients into one flat f32 buffer (``param.grad`` are views of it), the layout a
@@ -21,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import freeze
 from .headgraph import Ref, parse_head
 from .ops import TAPS3, SegSpec
 
@@ -31,9 +34,21 @@ MERGE = ((0, 0), (1, 0), (0, 1), (1, 1))                        # PatchMerging g
 USE_HIPGRAPH = os.environ.get("SODT_HIPGRAPH", "0") == "1"     # opt-in: see Engine._replay
 
 
+class _Yes:
+    def __getitem__(self, key):
+        return True
+
+
+class _EveryUnit:
+    """the freeze.UnitRecord of a plan without one (eval plans, plans built by hand): nothing is frozen"""
+    runs_bwd = saves = any_dx = any_wgrad = True
+    needs_dx = wgrad = _Yes()
+
+
 class Plan:
-    def __init__(self, B, S, dt, training, dev):
+    def __init__(self, B, S, dt, training, dev, fz=None):
         self.B, self.S, self.dt, self.training, self.dev = B, S, dt, training, dev
+        self.fz: Optional[freeze.FreezeRecord] = fz     # what the requires_grad flags leave of the backward (training plans of Engine.run)
         self.bufs: Dict[str, torch.Tensor] = {}
         self.bwd_marks: List[Tuple[int, int, int]] = []   # (index in bwd_main, first, last+1 element of flat_grad) of the
         #                                                   gradient buckets that are final at that launch (ddp overlap)
@@ -47,6 +62,26 @@ class Plan:
         self.sr = None                            # this plan's sr.SRBranch (Engine._sr_forward)
         self.enc_bwd_start: Optional[int] = None  # index in bwd_main where the head's backward ends and the encoder's begins
         self.enc_gin: Optional[list] = None       # [(buf, ld, off, c)]: where the head leaves d(f0), d(f1), d(f2)
+
+    def unit(self, name):
+        """the freeze.UnitRecord of unit `name`"""
+        return _EveryUnit if self.fz is None else self.fz.units[name]
+
+    def trainable(self, *names):
+        """whether any of these parameters takes a gradient"""
+        return True if self.fz is None else self.fz.trainable(*names)
+
+    def saves(self, name):
+        """whether the forward of unit `name` keeps what its backward reads"""
+        return self.training and self.unit(name).saves
+
+    def keep(self, save, name, kind, shape, dtype=None):
+        """A forward intermediate the backward reads back: the unit's own buffer `name` when it is saved (and in an eval plan, as
+        ever); in a training plan whose unit saves nothing, one scratch per kind and shape that every such unit shares (one unit's
+        forward runs at a time)."""
+        if save or not self.training:
+            return self.buf(name, shape, dtype)
+        return self.scratch("fwd." + kind, shape, dtype)
 
     def _cached(self, name, shape, dtype):
         """the buffer already allocated under `name`, or None; a hit with another shape or dtype is a bug of the caller"""
@@ -91,6 +126,16 @@ class Plan:
     def scratch(self, kind, shape, dtype=None, zero=False):
         """Backward scratch that every user of the same kind AND shape shares (one block's backward runs at a time)."""
         return self.buf(f"g.{kind}.{'x'.join(str(d) for d in shape)}", shape, dtype, zero)
+
+
+class _Plans(dict):
+    """Engine.plans: (B, S, dt, False) -> eval plan, (B, S, dt, True, freeze signature) -> training plan.  The four-entry key of a
+    training plan reads the plan with nothing frozen (signature 0), which is what it named before plans knew about freezing."""
+
+    def __missing__(self, key):
+        if len(key) == 4 and key[3] and key + (0,) in self:
+            return self[key + (0,)]
+        raise KeyError(key)
 
 
 # what _block_route chooses among (BlockRoute.attn / .mlp)
@@ -209,7 +254,11 @@ class Engine:
         self.sr = bool(getattr(model, "sr", False))
         self.head = parse_head(model)             # headgraph.HeadGraph: units, Upsample / Concat rules, Detect's input, SR taps
         self.det_name = f"detect.{self.head.nd}."
-        self.plans: Dict[Tuple, Plan] = {}
+        self.plans: Dict[Tuple, Plan] = _Plans()
+        self.unit_graph = freeze.unit_graph(list(self.params), self.head, self.sr)
+        self.unit_inputs = {u.name: u.inputs for u in self.unit_graph}
+        self._fz: Dict[tuple, freeze.FreezeRecord] = {}           # requires_grad bits (gradient order) -> record
+        self._was_frozen: frozenset = frozenset()                  # the frozen set of the latest backward (_claim_grads)
         self.probes_fwd: Optional[dict] = None    # bench.py: {call index: (start event, end event)}
         self.probes_bwd: Optional[dict] = None
         self.prep: Dict[torch.dtype, dict] = {}
@@ -236,30 +285,17 @@ class Engine:
 
     # ------------------------------------------------------------------ gradients: one flat f32 buffer
     def _build_grad_buffer(self):
-        order = [E + f"channel_embed_{c}.proj.weight" for c in "rgbi"] + [E + f"channel_embed_{c}.proj.bias" for c in "rgbi"]
-        order += [E + f"chan_block.norm{i}.weight" for i in range(1, 5)] + [E + f"chan_block.norm{i}.bias" for i in range(1, 5)]
-        # the rest in REVERSE order of completion in the backward, so that the buckets that become final first are
-        # contiguous slices at the end of the buffer (ddp.py): [front end | pos/patch embed | stage 1 | PatchMerging 1,
-        # neck 1 | stage 2 | PatchMerging 2, neck 2 | stage 3 | neck 3 | head]
-        groups = [E + "pos_embed", E + "patch_embed.", E + "stage1.", E + "pmerging1.", E + "neck1.", E + "stage2.",
-                  E + "pmerging2.", E + "neck2.", E + "stage3.", E + "neck3.", "detect.", "model_up."]
-        seen = set(order)
-        rest = []
-        for gname in groups:
-            rest += [n for n in self.params if n.startswith(gname) and n not in seen]
-            seen.update(rest)
-        rest += [n for n in self.params if n not in seen]      # nothing today; keeps unknown parameters reducible
-        self.grad_order = order + rest
-        offs, tot = {}, 0
-        for n in self.grad_order:
-            offs[n] = tot
-            tot += (self.params[n].numel() + 7) // 8 * 8      # every view 16-byte aligned in f32 AND in the bf16 mirror
+        # layout: freeze.grad_layout ([front end | pos/patch embed | stage 1 | ... | head | SR branch], reverse order of completion)
+        self.grad_order, offs, tot = freeze.grad_layout({n: p.numel() for n, p in self.params.items()})
+        self.fe_end = offs[self.grad_order[16]]          # the front end's sixteen gradients: [0, fe_end)
         self.flat_grad = torch.zeros(tot, device=self.dev, dtype=torch.float32)
         self.g: Dict[str, torch.Tensor] = {}
         for n in self.grad_order:
             p = self.params[n]
             self.g[n] = self.flat_grad[offs[n]: offs[n] + p.numel()].view(p.shape)
         self.grad_offsets = offs
+        self._claim = [(n, p, self.g[n], self.g[n].data_ptr()) for n, p in self.params.items()]      # _claim_grads walks this
+        self._ordered = [self.params[n] for n in self.grad_order]                                    # freeze_record reads these
         # first element of the buffer's tail that is complete before the stage-1 backward (see _backward_main)
         self.ddp_split = offs[next(n for n in self.grad_order if n.startswith(E + "pmerging1."))]
         self.ddp_split3 = offs[next(n for n in self.grad_order if n.startswith(E + "stage3."))]
@@ -315,17 +351,54 @@ class Engine:
                 raise RuntimeError(f"{n} no longer lives in the engine's flat parameter buffer (model.to()/.float()/.half() after the "
                                    "first forward re-allocates parameters): rebuild the engine with model._engine = None")
 
-    def _claim_grads(self):
-        """Make param.grad the views of the flat buffer; zero it when the grads were reset."""
+    def freeze_record(self) -> freeze.FreezeRecord:
+        """freeze.propagate for the parameters' requires_grad flags as they are now (one record per distinct set of flags)."""
+        bits = tuple([p.requires_grad for p in self._ordered])
+        fz = self._fz.get(bits)
+        if fz is None:
+            if len(self._fz) >= 64:
+                self._fz.clear()
+            frozen = [n for n, b in zip(self.grad_order, bits) if not b]
+            fz = self._fz[bits] = freeze.propagate(self.unit_graph, frozen, self.grad_order, self.grad_offsets, self.flat_grad.numel())
+        return fz
+
+    def _claim_grads(self, frozen=None):
+        """Make the trainable parameters' .grad the views of the flat buffer; returns whether the gradients were reset (the caller
+        zeroes the buffer).  frozen: the names the coming backward treats as frozen (default: requires_grad as it is now).  A
+        frozen parameter's .grad is never a view: torch leaves it None, so a view left from the time the parameter was trainable
+        is dropped and its slice of the buffer cleared.  Every frozen slice is zero when a backward returns, so a parameter that
+        was frozen at the latest backward takes its view back without counting as a reset."""
+        if frozen is None:
+            frozen = self.freeze_record().frozen
         fresh = False
-        for n, p in self.params.items():
-            v = self.g[n]
-            if p.grad is None:
+        dropped = []
+        held = claimed = 0
+        for n, p, v, ptr in self._claim:
+            g = p.grad
+            if n in frozen:
+                if g is not None and g.data_ptr() == ptr:
+                    p.grad = None
+                    dropped.append(n)
+            elif g is None:
                 p.grad = v
-                fresh = True
-            elif p.grad.data_ptr() != v.data_ptr():
+                claimed += 1
+                fresh = fresh or n not in self._was_frozen
+            elif g.data_ptr() != ptr:
                 raise RuntimeError(f"{n}.grad is not the engine's flat-buffer view; use optimizer.zero_grad(set_to_none=True) "
                                    "or leave .grad untouched between steps")
+            else:
+                held += 1
+        fresh = fresh or (claimed > 0 and held == 0)      # no trainable parameter held a gradient: nothing is being accumulated
+        self._was_frozen = frozen
+        if dropped and not fresh:
+            drop = set(dropped)
+            start = None
+            for n in self.grad_order + [None]:            # neighbours in the buffer: one memset per run
+                if n in drop:
+                    start = self.grad_offsets[n] if start is None else start
+                elif start is not None:
+                    ops.zero_(self.flat_grad[start: self.flat_grad.numel() if n is None else self.grad_offsets[n]])
+                    start = None
         return fresh
 
     # ------------------------------------------------------------------ prepared parameters
@@ -447,12 +520,16 @@ class Engine:
         if psb != self.pad_shifted_blocks:
             self.pad_shifted_blocks = psb
             self.plans.clear()                                   # recorded launch lists hold the routes of the other setting
-        key = (B, S, dt, training)
+        # a training plan belongs to one set of requires_grad flags (its launch lists and its workspace follow them), read here at
+        # every forward: freezing at an epoch boundary (Train.py:328-333) needs no call.  Eval plans save nothing and have no
+        # backward: one plan whatever the flags (an EMA copy is frozen throughout).
+        fz = self.freeze_record() if training else None
+        key = (B, S, dt, training, fz.signature) if training else (B, S, dt, training)
         plan = self.plans.pop(key, None)
         if plan is None:
             while len(self.plans) >= self.MAX_PLANS:
                 self.plans.pop(next(iter(self.plans)))          # dicts keep insertion order: the first key is the LRU one
-            plan = Plan(B, S, dt, training, self.dev)
+            plan = Plan(B, S, dt, training, self.dev, fz)
         self.plans[key] = plan                                   # (re)insert as most recently used
         out_sr = None
         if training and torch.is_grad_enabled():
@@ -686,18 +763,27 @@ class Engine:
         x_in, (B, H, W, Cc, ws, shift) = r.x_in, r.geo
         M = B * H * W
         bias_t = P["bias_t"][pre + "attn.relative_position_bias_table"]
-        xn1 = plan.buf(tag + ".xn1", (M, Cc))
-        st1 = plan.buf(tag + ".st1", (M, 2), torch.float32)
-        xm = plan.buf(tag + ".xm", (M, Cc))
-        xn2 = plan.buf(tag + ".xn2", (M, Cc))
-        st2 = plan.buf(tag + ".st2", (M, 2), torch.float32)
+        # what the backward of the attention half (sa) and of the MLP half (sm) read back: kept per block only where that half's
+        # backward runs (freeze.py); a frozen block below every trainable parameter runs the eval plan's launches
+        sa, sm = plan.saves(tag + ".attn"), plan.saves(tag + ".mlp")
+        if r.attn in (ATTN_FUSED_RC, ATTN_FUSED_SAVED) and plan.training and not (sa or sm):
+            xm = plan.keep(False, tag + ".xm", "xm", (M, Cc))
+            xn2 = plan.keep(False, tag + ".xn2", "xn2", (M, Cc))
+            ops.wmsa_block_fwd(x_in, r.wpk, xm, xn2, None, None, None, None, None, None, B, H, W, Cc, HEADS, ws, shift)
+            return xm, xn2
+        xn1 = plan.keep(sa, tag + ".xn1", "xn1", (M, Cc))
+        st1 = plan.keep(sa, tag + ".st1", "st1", (M, 2), torch.float32)
+        xm = plan.keep(sm, tag + ".xm", "xm", (M, Cc))
+        xn2 = plan.keep(sm, tag + ".xn2", "xn2", (M, Cc))
+        st2 = plan.keep(sm, tag + ".st2", "st2", (M, 2), torch.float32)
         if r.attn in (ATTN_FUSED_RC, ATTN_FUSED_SAVED):
             # LN1 + QKV + window attention + proj + residual + LN2 in ONE launch (csrc/wmsa_hg.hip / wmsa_block.hip); training also
             # writes what the backward needs: xn1, the attention output, the LayerNorm statistics and the window-major
-            # log-sum-exp (and q / k / v where the backward reads them back)
-            ao = plan.buf(tag + ".ao", (M, Cc))
-            qkvw = plan.buf(tag + ".qkvw", (M // 64, HEADS, 3, 64, Cc // HEADS)) if (plan.training and r.attn == ATTN_FUSED_SAVED) else None
-            lsew = plan.buf(tag + ".lsew", (M // 64, HEADS, 64), torch.float32)
+            # log-sum-exp (and q / k / v where the backward reads them back).  The launch saves all of it or nothing: one half
+            # that saves makes it save for both.
+            ao = plan.keep(sa, tag + ".ao", "ao", (M, Cc))
+            qkvw = plan.keep(sa, tag + ".qkvw", "qkvw", (M // 64, HEADS, 3, 64, Cc // HEADS)) if (plan.training and r.attn == ATTN_FUSED_SAVED) else None
+            lsew = plan.keep(sa, tag + ".lsew", "lsew", (M // 64, HEADS, 64), torch.float32)
             if plan.training:
                 ops.wmsa_block_fwd(x_in, r.wpk, xm, xn2, st1, st2, xn1, qkvw, lsew, ao, B, H, W, Cc, HEADS, ws, shift)
             else:
@@ -707,27 +793,27 @@ class Engine:
         if r.attn == ATTN_PADDED:
             Hp, Wp = r.pad
             Mp = B * Hp * Wp
-            qkv = plan.buf(tag + ".qkv", (Mp, 3 * Cc))
+            qkv = plan.keep(sa, tag + ".qkv", "qkv", (Mp, 3 * Cc))
             ops.gemm_nt([SegSpec(xn1, Cc, 0, 0, 0, 1, 0, H, W)], w[pre + "attn.qkv.weight"], qkv, Mp, 3 * Cc, Cc, spatial=(Hp, Wp),
                         bias=p[pre + "attn.qkv.bias"])
-            lse = plan.buf(tag + ".lse", (Mp, HEADS), torch.float32)
-            aop = plan.buf(tag + ".aop", (Mp, Cc))
+            lse = plan.keep(sa, tag + ".lse", "lse", (Mp, HEADS), torch.float32)
+            aop = plan.keep(sa, tag + ".aop", "aop", (Mp, Cc))
             ops.window_attn_fwd(qkv, bias_t, aop, lse, B, Hp, Wp, Cc, HEADS, ws, 0)
             ops.gemm_nt([SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, spatial=(H, W),
                         bias=p[pre + "attn.proj.bias"], resid=x_in)
         elif r.attn == ATTN_SHIFT_PAD:
             # every tensor on the unpadded grid: a pad key reads qkv.bias inside the kernel, a pad query is never computed
-            ao = plan.buf(tag + ".ao", (M, Cc))
-            qkv = plan.buf(tag + ".qkv", (M, 3 * Cc))
+            ao = plan.keep(sa, tag + ".ao", "ao", (M, Cc))
+            qkv = plan.keep(sa, tag + ".qkv", "qkv", (M, 3 * Cc))
             ops.gemm_nt([SegSpec(xn1)], w[pre + "attn.qkv.weight"], qkv, M, 3 * Cc, Cc, bias=p[pre + "attn.qkv.bias"])
-            lse = plan.buf(tag + ".lse", (M, HEADS), torch.float32)
+            lse = plan.keep(sa, tag + ".lse", "lse", (M, HEADS), torch.float32)
             ops.window_attn_sp_fwd(qkv, p[pre + "attn.qkv.bias"], bias_t, ao, lse, B, H, W, Cc, HEADS, ws, shift)
             ops.gemm_nt([SegSpec(ao)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, bias=p[pre + "attn.proj.bias"], resid=x_in)
         else:
-            ao = plan.buf(tag + ".ao", (M, Cc))
-            qkv = plan.buf(tag + ".qkv", (M, 3 * Cc))
+            ao = plan.keep(sa, tag + ".ao", "ao", (M, Cc))
+            qkv = plan.keep(sa, tag + ".qkv", "qkv", (M, 3 * Cc))
             ops.gemm_nt([SegSpec(xn1)], w[pre + "attn.qkv.weight"], qkv, M, 3 * Cc, Cc, bias=p[pre + "attn.qkv.bias"])
-            lse = plan.buf(tag + ".lse", (M, HEADS), torch.float32)
+            lse = plan.keep(sa, tag + ".lse", "lse", (M, HEADS), torch.float32)
             ops.window_attn_fwd(qkv, bias_t, ao, lse, B, H, W, Cc, HEADS, ws, shift)
             ops.gemm_nt([SegSpec(ao)], w[pre + "attn.proj.weight"], xm, M, Cc, Cc, bias=p[pre + "attn.proj.bias"], resid=x_in)
         ops.layernorm_fwd(xm, p[pre + "norm2.weight"], p[pre + "norm2.bias"], xn2, st2, M, Cc)
@@ -740,19 +826,20 @@ class Engine:
         B, H, W, Cc, _, _ = r.geo
         M = B * H * W
         xo = plan.buf(tag + ".xo", (M, Cc))
+        sm = plan.saves(tag + ".mlp")
         if r.mlp == MLP_FUSED:
             # fc1 + GELU + fc2 + residual in ONE launch (csrc/mlp.hip): the 4C-wide hidden activation leaves the CU only in training,
             # as GELU(h) for fc2's weight gradient (the backward recomputes h inside the dh GEMM, as below)
-            ha = plan.buf(tag + ".ha", (M, 4 * Cc)) if plan.training else None
+            ha = plan.buf(tag + ".ha", (M, 4 * Cc)) if sm else None
             ops.mlp_fwd(xn2, w[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], w[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"],
                         xm, xo, ha, M, Cc)
         elif r.mlp in (MLP_LIN_RC, MLP_LIN_SAVED):
-            ha = plan.buf(tag + ".ha", (M, 4 * Cc))
+            ha = plan.keep(sm, tag + ".ha", "ha", (M, 4 * Cc))
             if r.mlp == MLP_LIN_RC:
                 # only GELU(h) is written; backward recomputes h inside the dh GEMM
                 ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], ha, M, 4 * Cc, Cc, bias=p[pre + "mlp.fc1.bias"], gelu_only=True)
             else:
-                hp = plan.buf(tag + ".hp", (M, 4 * Cc))
+                hp = plan.keep(sm, tag + ".hp", "hp", (M, 4 * Cc))
                 ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], hp, M, 4 * Cc, Cc, bias=p[pre + "mlp.fc1.bias"], gelu_out=ha)
             ops.gemm_nt([SegSpec(ha)], w[pre + "mlp.fc2.weight"], xo, M, Cc, 4 * Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
         else:
@@ -764,11 +851,11 @@ class Engine:
                                     cm["weff"], cm["weffT"], cm["beff"], cm["vtap"], Cc)
                 src, wc, bc = xn2, cm["weff"], cm["beff"]
             else:
-                src = plan.buf(tag + ".u", (M, Cc))
+                src = plan.keep(sm, tag + ".u", "u", (M, Cc))
                 ops.gemm_nt([SegSpec(xn2)], w[pre + "mlp.fc1.weight"], src, M, Cc, Cc, bias=p[pre + "mlp.fc1.bias"])
                 wc, bc = w[pre + "mlp.conv1.weight"], p[pre + "mlp.conv1.bias"]
-            cp = plan.buf(tag + ".cp", (M, Cc))
-            ca = plan.buf(tag + ".ca", (M, Cc))
+            cp = plan.keep(sm, tag + ".cp", "cp", (M, Cc))
+            ca = plan.keep(sm, tag + ".ca", "ca", (M, Cc))
             segs = [SegSpec(src, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
             ops.gemm_nt(segs, wc, cp, M, Cc, 4 * Cc, spatial=(H, W), bias=bc, gelu_out=ca)
             if r.mlp == MLP_FOLD:
@@ -776,26 +863,36 @@ class Engine:
             ops.gemm_nt([SegSpec(ca)], w[pre + "mlp.fc2.weight"], xo, M, Cc, Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
         return xo
 
-    def _linear_bwd(self, P, name, dY, X, dX, M, N, K, *, bias=True, sq=False, dgelu_aux=None, ldy=None, y_off=0, resid=None):
+    def _linear_bwd(self, P, name, dY, X, dX, M, N, K, *, bias=True, sq=False, dgelu_aux=None, ldy=None, y_off=0, resid=None,
+                    plan=None, need_dx=True):
         """Backward of one nn.Linear / 1x1 convolution `name` ([N][K] weight): dW (and dbias) += dY^T X by sodt_gemm_tn, then
         dX = dY W [* gelu'(dgelu_aux)] [+ resid] by sodt_gemm_nt; dY may be N columns at y_off of a wider buffer.  sq: try the
         square one-launch form first (csrc/linbwd.hip: both from one read of dY; ops.linear_bwd_sq returns False where the entry
-        point refuses the layer, and the two launches run instead)."""
+        point refuses the layer, and the two launches run instead).  plan: its frozen parameters take no weight-gradient launch (a
+        frozen weight AND bias leave the plain sodt_gemm_nt); need_dx False: nobody reads dX, only the parameter gradients run."""
         gw, gb, wT = self.g[name + ".weight"], self.g[name + ".bias"] if bias else None, P["wT"][name + ".weight"]
-        if sq and ops.linear_bwd_sq(dY, X, wT, dX, gw, M, dbias=gb, dgelu_aux=dgelu_aux):
+        wg = plan is None or plan.trainable(name + ".weight", *([name + ".bias"] if bias else []))
+        if sq and wg and need_dx and ops.linear_bwd_sq(dY, X, wT, dX, gw, M, dbias=gb, dgelu_aux=dgelu_aux):
             return
-        ops.gemm_tn(dY, [SegSpec(X)], gw, M, N, K, dbias=gb, ldy=ldy, y_off=y_off)
-        ops.gemm_nt([SegSpec(dY, N, y_off)], wT, dX, M, K, N, dgelu_aux=dgelu_aux, resid=resid)
+        if wg:
+            ops.gemm_tn(dY, [SegSpec(X)], gw, M, N, K, dbias=gb, ldy=ldy, y_off=y_off)
+        if need_dx:
+            ops.gemm_nt([SegSpec(dY, N, y_off)], wT, dX, M, K, N, dgelu_aux=dgelu_aux, resid=resid)
 
     def _block_bwd(self, plan, P, tag, blk, dY, dX):
-        """dY: gradient wrt the block output; writes the gradient wrt the block input into dX."""
+        """dY: gradient wrt the block output; writes the gradient wrt the block input into dX (where the input needs one)."""
         ops.set_tag(tag + ".bwd")
         r = plan.saved[tag]
+        if not plan.unit(tag + ".mlp").runs_bwd:
+            return
         dxm, dxn = self._mlp_bwd(plan, P, tag, r, dY)
-        self._attn_bwd(plan, P, tag, r, dxm, dxn, dX)
+        if plan.unit(tag + ".attn").runs_bwd:
+            self._attn_bwd(plan, P, tag, r, dxm, dxn, dX)
 
     def _mlp_bwd(self, plan, P, tag, r: BlockRoute, dY):
-        """MLP and LayerNorm-2 backward; returns (dxm: gradient wrt xm, dxn: scratch the attention backward goes on with)."""
+        """MLP and LayerNorm-2 backward; returns (dxm: gradient wrt xm, dxn: scratch the attention backward goes on with).  Frozen
+        parameters: a stand-alone weight-gradient launch whose every output is frozen is not issued; where the attention half has no
+        backward (nothing trainable at or below it) the chain stops at the lowest trainable parameter of this half."""
         p, wT, g, b = self.params, P["wT"], self.g, plan.bufs
         pre = E + tag + "."
         B, H, W, Cc, _, _ = r.geo
@@ -804,45 +901,56 @@ class Engine:
         dxn = plan.scratch("dxn", (M, Cc))
         dxm = plan.scratch("dxm", (M, Cc))
         sq = self.use_fused_linbwd and r.sq_ok          # a backward-only switch: read live
+        T = plan.trainable
+        ln2 = plan.unit(tag + ".attn").runs_bwd or T(pre + "norm2.weight", pre + "norm2.bias")     # d(xn2) and the LayerNorm-2 backward
+        fc1 = T(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
         if r.mlp in (MLP_FUSED, MLP_LIN_RC, MLP_LIN_SAVED):
             ha = b[tag + ".ha"]
             dh = plan.scratch("dh", (M, 4 * Cc))
             if r.mlp == MLP_LIN_SAVED:
-                self._linear_bwd(P, pre + "mlp.fc2", dY, ha, dh, M, Cc, 4 * Cc, dgelu_aux=b[tag + ".hp"])
+                self._linear_bwd(P, pre + "mlp.fc2", dY, ha, dh, M, Cc, 4 * Cc, dgelu_aux=b[tag + ".hp"], plan=plan, need_dx=ln2 or fc1)
             else:       # dh = (dY fc2.weight) * gelu'(xn2 fc1.weight^T + b1): pre-activation recomputed in the first K half
-                ops.gemm_tn(dY, [SegSpec(ha)], g[pre + "mlp.fc2.weight"], M, Cc, 4 * Cc, dbias=g[pre + "mlp.fc2.bias"])
-                ops.gemm_nt([SegSpec(xn2), SegSpec(dY)], P["wcat"][pre + "mlp.fc1.weight"], dh, M, 4 * Cc, 2 * Cc,
-                            bias=p[pre + "mlp.fc1.bias"], dgelu_rc=True)
-            self._linear_bwd(P, pre + "mlp.fc1", dh, xn2, dxn, M, 4 * Cc, Cc)
+                if T(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias"):
+                    ops.gemm_tn(dY, [SegSpec(ha)], g[pre + "mlp.fc2.weight"], M, Cc, 4 * Cc, dbias=g[pre + "mlp.fc2.bias"])
+                if ln2 or fc1:
+                    ops.gemm_nt([SegSpec(xn2), SegSpec(dY)], P["wcat"][pre + "mlp.fc1.weight"], dh, M, 4 * Cc, 2 * Cc,
+                                bias=p[pre + "mlp.fc1.bias"], dgelu_rc=True)
+            self._linear_bwd(P, pre + "mlp.fc1", dh, xn2, dxn, M, 4 * Cc, Cc, plan=plan, need_dx=ln2)
         else:
             cp, ca = b[tag + ".cp"], b[tag + ".ca"]
             dc = plan.scratch("dc", (M, Cc))
-            self._linear_bwd(P, pre + "mlp.fc2", dY, ca, dc, M, Cc, Cc, sq=sq, dgelu_aux=cp)
+            conv1 = T(pre + "mlp.conv1.weight", pre + "mlp.conv1.bias")
+            self._linear_bwd(P, pre + "mlp.fc2", dY, ca, dc, M, Cc, Cc, sq=sq, dgelu_aux=cp, plan=plan, need_dx=ln2 or fc1 or conv1)
             bsegs = [SegSpec(dc, Cc, 0, -dy, -dx, 1, 0, H, W) for (dy, dx) in TAPS2]
             if r.mlp == MLP_FOLD:
                 # d(Weff) = dc^T xn2(taps) (+ the column sums of dc), then the parameter gradients of fc1 / conv1 by the chain rule;
                 # d(xn2) comes from ONE tap GEMM with the composed weights (no du, no du W1)
                 cm = P["cmlp"][pre]
-                scr = plan.scratch("cmlp", (Cc * 4 * Cc + 4 * Cc,), torch.float32)
-                dweff, colsum, bs = scr[: Cc * 4 * Cc].view(Cc, 4 * Cc), scr[Cc * 4 * Cc: Cc * 4 * Cc + Cc], scr[Cc * 4 * Cc + Cc:].view(3, Cc)
-                ops.zero_(scr)
-                segs = [SegSpec(xn2, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-                ops.gemm_tn(dc, segs, dweff, M, Cc, 4 * Cc, spatial=(H, W), dbias=colsum)
-                ops.convmlp_border_sums(dc, bs, B, H, W, Cc)
-                ops.convmlp_decompose(dweff, colsum, bs, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"],
-                                      g[pre + "mlp.conv1.weight"], g[pre + "mlp.conv1.bias"], g[pre + "mlp.fc1.weight"], g[pre + "mlp.fc1.bias"], Cc)
-                ops.gemm_nt(bsegs, cm["weffT"], dxn, M, Cc, 4 * Cc, spatial=(H, W))
+                if fc1 or conv1:
+                    scr = plan.scratch("cmlp", (Cc * 4 * Cc + 4 * Cc,), torch.float32)
+                    dweff, colsum, bs = scr[: Cc * 4 * Cc].view(Cc, 4 * Cc), scr[Cc * 4 * Cc: Cc * 4 * Cc + Cc], scr[Cc * 4 * Cc + Cc:].view(3, Cc)
+                    ops.zero_(scr)
+                    segs = [SegSpec(xn2, Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
+                    ops.gemm_tn(dc, segs, dweff, M, Cc, 4 * Cc, spatial=(H, W), dbias=colsum)
+                    ops.convmlp_border_sums(dc, bs, B, H, W, Cc)
+                    ops.convmlp_decompose(dweff, colsum, bs, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], p[pre + "mlp.conv1.weight"],
+                                          g[pre + "mlp.conv1.weight"], g[pre + "mlp.conv1.bias"], g[pre + "mlp.fc1.weight"], g[pre + "mlp.fc1.bias"], Cc)
+                if ln2:
+                    ops.gemm_nt(bsegs, cm["weffT"], dxn, M, Cc, 4 * Cc, spatial=(H, W))
             else:
                 du = plan.scratch("du", (M, Cc))
                 segs = [SegSpec(b[tag + ".u"], Cc, 0, dy, dx, 1, 0, H, W) for (dy, dx) in TAPS2]
-                ops.gemm_tn(dc, segs, g[pre + "mlp.conv1.weight"], M, Cc, 4 * Cc, spatial=(H, W), dbias=g[pre + "mlp.conv1.bias"],
-                            kperm=(Cc, 4))
-                ops.gemm_nt(bsegs, wT[pre + "mlp.conv1.weight"], du, M, Cc, 4 * Cc, spatial=(H, W))
-                self._linear_bwd(P, pre + "mlp.fc1", du, xn2, dxn, M, Cc, Cc)
+                if conv1:
+                    ops.gemm_tn(dc, segs, g[pre + "mlp.conv1.weight"], M, Cc, 4 * Cc, spatial=(H, W), dbias=g[pre + "mlp.conv1.bias"],
+                                kperm=(Cc, 4))
+                if ln2 or fc1:
+                    ops.gemm_nt(bsegs, wT[pre + "mlp.conv1.weight"], du, M, Cc, 4 * Cc, spatial=(H, W))
+                self._linear_bwd(P, pre + "mlp.fc1", du, xn2, dxn, M, Cc, Cc, plan=plan, need_dx=ln2)
         # dxn = d(xn2); the LayerNorm-2 backward adds the residual path's dY.  (Rounds 4-5 carried a GEMM with the LayerNorm backward
         # as its epilogue for the 192-column case: slower than these two launches, removed in round 6 - profiles/r04_lnfold_ab.md,
         # DESIGN.md section 5.)
-        ops.layernorm_bwd(dxn, xm, b[tag + ".st2"], p[pre + "norm2.weight"], dY, dxm, g[pre + "norm2.weight"], g[pre + "norm2.bias"], M, Cc)
+        if ln2:
+            ops.layernorm_bwd(dxn, xm, b[tag + ".st2"], p[pre + "norm2.weight"], dY, dxm, g[pre + "norm2.weight"], g[pre + "norm2.bias"], M, Cc)
         return dxm, dxn
 
     def _attn_bwd(self, plan, P, tag, r: BlockRoute, dxm, dxn, dX):
@@ -850,7 +958,8 @@ class Engine:
         d(xn1)).  The padded arm is the backward of an UNSHIFTED block whose resolution is not a multiple of its window (see
         _block_route): the projection's input gradient lands on the padded grid (zeros outside: the crop's adjoint), the attention
         backward runs on it, qkv.weight sees zero rows for the pad tokens while qkv.bias collects their gradient (their q / k / v
-        ARE the bias), and the input gradient is read back cropped."""
+        ARE the bias), and the input gradient is read back cropped.  Frozen parameters as in _mlp_bwd: where the block's input needs
+        no gradient the chain stops at the lowest trainable parameter."""
         p, wT, g, b = self.params, P["wT"], self.g, plan.bufs
         pre = E + tag + "."
         B, H, W, Cc, ws, shift = r.geo
@@ -858,42 +967,54 @@ class Engine:
         xn1 = b[tag + ".xn1"]
         bias_t = P["bias_t"][pre + "attn.relative_position_bias_table"]
         L2 = 2 * ws - 1
+        T = plan.trainable
+        ln1 = plan.unit(tag + ".attn").any_dx or T(pre + "norm1.weight", pre + "norm1.bias")       # d(xn1) and the LayerNorm-1 backward
+        qkvg = T(pre + "attn.qkv.weight", pre + "attn.qkv.bias")
+        attn = ln1 or qkvg or T(pre + "attn.relative_position_bias_table")                        # the attention backward itself
         if r.attn == ATTN_PADDED:
             Hp, Wp = r.pad
             Mp = B * Hp * Wp
             aop = b[tag + ".aop"]
-            ops.gemm_tn(dxm, [SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], g[pre + "attn.proj.weight"], M, Cc, Cc, spatial=(H, W),
-                        dbias=g[pre + "attn.proj.bias"])
-            daop = plan.scratch("daop", (Mp, Cc))
-            ops.gemm_nt([SegSpec(dxm, Cc, 0, 0, 0, 1, 0, H, W)], wT[pre + "attn.proj.weight"], daop, Mp, Cc, Cc, spatial=(Hp, Wp))
-            dqkv = plan.scratch("dqkvp", (Mp, 3 * Cc))
-            dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
-            scratch = plan.scratch("attn_scratchp", (Mp * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
-            ops.window_attn_bwd(b[tag + ".qkv"], bias_t, aop, daop, b[tag + ".lse"], dqkv, dbt, scratch, B, Hp, Wp, Cc, HEADS, ws, 0)
-            ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
-            ops.gemm_tn(dqkv, [SegSpec(xn1, Cc, 0, 0, 0, 1, 0, H, W)], g[pre + "attn.qkv.weight"], Mp, 3 * Cc, Cc,
-                        spatial=(Hp, Wp), dbias=g[pre + "attn.qkv.bias"])
-            ops.gemm_nt([SegSpec(dqkv, 3 * Cc, 0, 0, 0, 1, 0, Hp, Wp)], wT[pre + "attn.qkv.weight"], dxn, M, Cc, 3 * Cc, spatial=(H, W))
+            if T(pre + "attn.proj.weight", pre + "attn.proj.bias"):
+                ops.gemm_tn(dxm, [SegSpec(aop, Cc, 0, 0, 0, 1, 0, Hp, Wp)], g[pre + "attn.proj.weight"], M, Cc, Cc, spatial=(H, W),
+                            dbias=g[pre + "attn.proj.bias"])
+            if attn:
+                daop = plan.scratch("daop", (Mp, Cc))
+                ops.gemm_nt([SegSpec(dxm, Cc, 0, 0, 0, 1, 0, H, W)], wT[pre + "attn.proj.weight"], daop, Mp, Cc, Cc, spatial=(Hp, Wp))
+                dqkv = plan.scratch("dqkvp", (Mp, 3 * Cc))
+                dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
+                scratch = plan.scratch("attn_scratchp", (Mp * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
+                ops.window_attn_bwd(b[tag + ".qkv"], bias_t, aop, daop, b[tag + ".lse"], dqkv, dbt, scratch, B, Hp, Wp, Cc, HEADS, ws, 0)
+                # (always: the transposition also clears dbt, which the next block's attention backward adds into)
+                ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
+                if qkvg:
+                    ops.gemm_tn(dqkv, [SegSpec(xn1, Cc, 0, 0, 0, 1, 0, H, W)], g[pre + "attn.qkv.weight"], Mp, 3 * Cc, Cc,
+                                spatial=(Hp, Wp), dbias=g[pre + "attn.qkv.bias"])
+                if ln1:
+                    ops.gemm_nt([SegSpec(dqkv, 3 * Cc, 0, 0, 0, 1, 0, Hp, Wp)], wT[pre + "attn.qkv.weight"], dxn, M, Cc, 3 * Cc, spatial=(H, W))
         else:
             ao, dao = b[tag + ".ao"], dxn
-            self._linear_bwd(P, pre + "attn.proj", dxm, ao, dao, M, Cc, Cc, sq=self.use_fused_linbwd and r.sq_ok)
-            dqkv = plan.scratch("dqkv", (M, 3 * Cc))
-            dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
-            if r.attn == ATTN_FUSED_RC:
-                ops.wmsa_block_bwd(xn1, r.wpk, bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
-            elif r.attn == ATTN_FUSED_SAVED:
-                ops.window_attn_bwd_wm(b[tag + ".qkvw"], bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
-            elif r.attn == ATTN_SHIFT_PAD:
-                # the pad keys' k / v gradient belongs to qkv.bias (their k / v ARE the bias): added there by the kernel, beside the
-                # column sums of dqkv the linear backward below adds
-                ops.window_attn_sp_bwd(b[tag + ".qkv"], p[pre + "attn.qkv.bias"], bias_t, ao, dao, b[tag + ".lse"], dqkv,
-                                       g[pre + "attn.qkv.bias"], dbt, B, H, W, Cc, HEADS, ws, shift)
-            else:
-                scratch = plan.scratch("attn_scratch", (M * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
-                ops.window_attn_bwd(b[tag + ".qkv"], bias_t, ao, dao, b[tag + ".lse"], dqkv, dbt, scratch, B, H, W, Cc, HEADS, ws, shift)
-            ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
-            self._linear_bwd(P, pre + "attn.qkv", dqkv, xn1, dxn, M, 3 * Cc, Cc)
-        ops.layernorm_bwd(dxn, r.x_in, b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"], g[pre + "norm1.bias"], M, Cc)
+            self._linear_bwd(P, pre + "attn.proj", dxm, ao, dao, M, Cc, Cc, sq=self.use_fused_linbwd and r.sq_ok, plan=plan, need_dx=attn)
+            if attn:
+                dqkv = plan.scratch("dqkv", (M, 3 * Cc))
+                dbt = plan.scratch("dbt", (HEADS, L2 * L2), torch.float32, zero=True)
+                if r.attn == ATTN_FUSED_RC:
+                    ops.wmsa_block_bwd(xn1, r.wpk, bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
+                elif r.attn == ATTN_FUSED_SAVED:
+                    ops.window_attn_bwd_wm(b[tag + ".qkvw"], bias_t, dao, b[tag + ".lsew"], dqkv, dbt, B, H, W, Cc, HEADS, ws, shift)
+                elif r.attn == ATTN_SHIFT_PAD:
+                    # the pad keys' k / v gradient belongs to qkv.bias (their k / v ARE the bias): added there by the kernel, beside the
+                    # column sums of dqkv the linear backward below adds
+                    ops.window_attn_sp_bwd(b[tag + ".qkv"], p[pre + "attn.qkv.bias"], bias_t, ao, dao, b[tag + ".lse"], dqkv,
+                                           g[pre + "attn.qkv.bias"], dbt, B, H, W, Cc, HEADS, ws, shift)
+                else:
+                    scratch = plan.scratch("attn_scratch", (M * (Cc + HEADS),), torch.float32, zero=True) if r.zscratch else None
+                    ops.window_attn_bwd(b[tag + ".qkv"], bias_t, ao, dao, b[tag + ".lse"], dqkv, dbt, scratch, B, H, W, Cc, HEADS, ws, shift)
+                # (always: the transposition also clears dbt, which the next block's attention backward adds into)
+                ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
+                self._linear_bwd(P, pre + "attn.qkv", dqkv, xn1, dxn, M, 3 * Cc, Cc, plan=plan, need_dx=ln1)
+        if ln1:
+            ops.layernorm_bwd(dxn, r.x_in, b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"], g[pre + "norm1.bias"], M, Cc)
 
     # ------------------------------------------------------------------ PatchMerging
     def _merge_fwd(self, plan, P, tag, x, B, H, W, Cc):
@@ -901,11 +1022,12 @@ class Engine:
         p, w = self.params, P["w"]
         pre = E + tag + "."
         M2 = B * (H // 2) * (W // 2)
-        z = plan.buf(tag + ".z", (M2, 2 * Cc))
+        sv = plan.saves(tag)
+        z = plan.keep(sv, tag + ".z", "z", (M2, 2 * Cc))
         segs = [SegSpec(x, Cc, 0, dy, dx, 2, 0, H, W) for (dy, dx) in MERGE]
         ops.gemm_nt(segs, w[pre + "reduction.weight"], z, M2, 2 * Cc, 4 * Cc, spatial=(H // 2, W // 2))
         y = plan.buf(tag + ".y", (M2, 2 * Cc))
-        st = plan.buf(tag + ".st", (M2, 2), torch.float32)
+        st = plan.keep(sv, tag + ".st", "st", (M2, 2), torch.float32)
         ops.layernorm_fwd(z, p[pre + "norm.weight"], p[pre + "norm.bias"], y, st, M2, 2 * Cc)
         plan.saved[tag] = dict(x=x, geo=(B, H, W, Cc))
         return y
@@ -920,7 +1042,10 @@ class Engine:
         ops.layernorm_bwd(dY, b[tag + ".z"], b[tag + ".st"], p[pre + "norm.weight"], None, dz, g[pre + "norm.weight"],
                           g[pre + "norm.bias"], M2, 2 * Cc)
         segs = [SegSpec(sv["x"], Cc, 0, dy, dx, 2, 0, H, W) for (dy, dx) in MERGE]
-        ops.gemm_tn(dz, segs, g[pre + "reduction.weight"], M2, 2 * Cc, 4 * Cc, spatial=(H // 2, W // 2))
+        if plan.trainable(pre + "reduction.weight"):
+            ops.gemm_tn(dz, segs, g[pre + "reduction.weight"], M2, 2 * Cc, 4 * Cc, spatial=(H // 2, W // 2))
+        if not plan.unit(tag).any_dx:
+            return
         for tap, (dy, dx) in enumerate(MERGE):   # the four taps tile the input grid exactly once
             ops.gemm_nt([SegSpec(dz, 2 * Cc, 0, 0, 0, 1, 0, H // 2, W // 2)], wT[pre + "reduction.weight"], dX, M2, Cc, 2 * Cc,
                         spatial=(H // 2, W // 2), w_off=tap * Cc * 2 * Cc, oscatter=(2, dy, dx, H, W))
@@ -934,14 +1059,16 @@ class Engine:
         y = plan.buf(tag + ".y", (M, Cout)) if out is None else out
         ldy = y.shape[-1]
         wname = pname + "conv.weight"
-        direct = bool(plan.training and not self.fused and self._direct3(plan, segs, K, Cout, k))
+        sv = plan.saves(tag.split(".")[0])        # (tag: the head unit "h3", or one of its convolutions "h3.cv1")
+        direct = bool(sv and not self.fused and self._direct3(plan, segs, K, Cout, k))
         if self.fused:
             ones = P["ones"].setdefault(Cout, torch.ones(Cout, device=self.dev))
             ops.gemm_nt(segs, w[wname], y, M, Cout, K, spatial=spatial, affine=(ones, p[pname + "conv.bias"]), ldc=ldy)
         elif plan.training:
-            z = plan.buf(tag + ".z", (M, Cout))
+            # (a unit that saves nothing still normalises with the batch statistics and moves the running ones: model.train())
+            z = plan.keep(sv, tag + ".z", "z", (M, Cout))
             stats = plan.zbuf("f", tag + ".stats", (L.STATS_REPL, 2, Cout), torch.float64)   # zeroed with the pool (_forward_main)
-            mr = plan.buf(tag + ".mr", (2, Cout), torch.float32)
+            mr = plan.keep(sv, tag + ".mr", "mr", (2, Cout), torch.float32)
             if direct:
                 # the 3x3 at 64 -> 64 channels of the stride-4 C3's Bottleneck: the direct kernel reads its input once (csrc/conv3.hip;
                 # the nine-segment GEMM ran at 0.11-0.15 of its HBM roofline), the batch statistics come from the stored output
@@ -982,7 +1109,9 @@ class Engine:
         ops.bn_silu_bwd_apply(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, dz,
                               g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off)
         cin = K // (k * k)
-        if sv.direct:
+        if not plan.trainable(pname + "conv.weight"):
+            pass
+        elif sv.direct:
             H, W = sv.spatial
             scr = plan.buf("g.c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
             ops.conv3_c64_wgrad(dz, sv.segs[4].t, g[pname + "conv.weight"], None, scr, M // (H * W), H, W)
@@ -1004,17 +1133,19 @@ class Engine:
         return out
 
     def _c3_bwd(self, plan, P, tag, dout, ldd, d_off):
-        """returns d(concatenated input) [M][c1]."""
+        """returns d(concatenated input) [M][c1], or None where no input of the unit needs a gradient."""
         wT = P["wT"]
+        dx = plan.unit(tag).any_dx
         sv = plan.saved[tag]
         M, c1, c2, (H, W), pname = sv["M"], sv["c1"], sv["c2"], sv["spatial"], sv["pname"]
         c_ = c2 // 2
         dz3 = self._conv_bwd(plan, tag + ".cv3", dout, ldd, d_off)
         dcat = plan.buf(tag + ".dcat", (M, 2 * c_))
         ops.gemm_nt([SegSpec(dz3)], wT[pname + "cv3.conv.weight"], dcat, M, 2 * c_, c2)
-        din = plan.buf(tag + ".din", (M, c1))
+        din = plan.buf(tag + ".din", (M, c1)) if dx else None
         dzb = self._conv_bwd(plan, tag + ".cv2", dcat, 2 * c_, c_)
-        ops.gemm_nt([SegSpec(dzb)], wT[pname + "cv2.conv.weight"], din, M, c1, c_)
+        if dx:
+            ops.gemm_nt([SegSpec(dzb)], wT[pname + "cv2.conv.weight"], din, M, c1, c_)
         dza3 = self._conv_bwd(plan, tag + ".m2", dcat, 2 * c_, 0)
         da = plan.buf(tag + ".da", (M, c_))
         if plan.saved[tag + ".m2"].direct:
@@ -1025,7 +1156,8 @@ class Engine:
         dza2 = self._conv_bwd(plan, tag + ".m1", da, c_, 0)
         ops.gemm_nt([SegSpec(dza2)], wT[pname + "m.0.cv1.conv.weight"], da, M, c_, c_)
         dza1 = self._conv_bwd(plan, tag + ".cv1", da, c_, 0)
-        ops.gemm_nt([SegSpec(dza1)], wT[pname + "cv1.conv.weight"], din, M, c1, c_, resid=din)
+        if dx:
+            ops.gemm_nt([SegSpec(dza1)], wT[pname + "cv1.conv.weight"], din, M, c1, c_, resid=din)
         return din
 
     # ------------------------------------------------------------------ SPP (common.py:129-140)
@@ -1037,7 +1169,7 @@ class Engine:
         H, W = spatial
         cat = plan.buf(tag + ".cat", (M, 4 * c_))
         self._conv_fwd(plan, P, tag + ".cv1", pname + "cv1.", segs, spatial if any(s_.shr or s_.Hi for s_ in segs) else None, M, c1, c_, 1, out=cat)
-        arg = plan.buf(tag + ".arg", (3, M, c_), torch.uint8) if plan.training else None
+        arg = plan.buf(tag + ".arg", (3, M, c_), torch.uint8) if plan.saves(tag) else None
         for i in range(3):                                   # m5, m9 = m5 o m5, m13 = m5 o m5 o m5 into the next slices
             ops.maxpool5_fwd(cat, cat, arg[i] if arg is not None else None, B, H, W, c_, ldx=4 * c_, ldy=4 * c_, x_off=i * c_,
                              y_off=(i + 1) * c_)
@@ -1046,7 +1178,7 @@ class Engine:
         return out
 
     def _spp_bwd(self, plan, P, tag, dout, ldd, d_off):
-        """returns d(input) [M][c1]."""
+        """returns d(input) [M][c1], or None where the input needs no gradient."""
         wT, b = P["wT"], plan.bufs
         sv = plan.saved[tag]
         M, c1, c2, (H, W), pname, B = sv["M"], sv["c1"], sv["c2"], sv["spatial"], sv["pname"], sv["B"]
@@ -1058,6 +1190,8 @@ class Engine:
             ops.maxpool5_bwd(dcat, b[tag + ".arg"][i], dcat, B, H, W, c_, lddy=4 * c_, lddx=4 * c_, dy_off=(i + 1) * c_, dx_off=i * c_,
                              accumulate=True)
         dz1 = self._conv_bwd(plan, tag + ".cv1", dcat, 4 * c_, 0)
+        if not plan.unit(tag).any_dx:
+            return None
         din = plan.buf(tag + ".din", (M, c1))
         ops.gemm_nt([SegSpec(dz1)], wT[pname + "cv1.conv.weight"], din, M, c1, c_)
         return din
@@ -1091,11 +1225,16 @@ class Engine:
         """SR gradients: parameters into the flat buffer, inputs into plan.sr's dense buffers (zero when the SR output took no part
         in the loss); the recorded head backward adds them to the tapped features' gradients (_backward_main: sr_extra)."""
         br = plan.sr
+        u = plan.unit("model_up")
+        if not u.runs_bwd:
+            return
         if dsr is None:
             for k in ("g.low", "g.x"):
                 if k in br.bufs:
                     ops.zero_(br.bufs[k])
             return
+        # the branch's frozen convolutions take no weight-gradient launch; taps that need no gradient take no input gradient
+        br.trainable, br.need_dx = plan.trainable, u.any_dx
         br.backward(dsr)
 
     def _sr_extra(self, plan: Plan):
@@ -1137,17 +1276,22 @@ class Engine:
         B, S = plan.B, plan.S
         t = S // 4
         T1 = B * t * t
-        fresh = self._claim_grads()
+        fz = plan.fz
+        fresh = self._claim_grads(None if fz is None else fz.frozen)
         if fresh:
             ops.zero_(self.flat_grad)
+        if fz is not None and not fz.any_bwd:
+            return                                   # everything frozen: no gradient to compute, nothing to reduce
+        first = 0 if fz is None else fz.first_trainable_offset      # the frozen head of the buffer is zero on every rank
         if self.ddp is not None:
             self.ddp.begin_backward(self.flat_grad, fresh)
         # (1) Detect backward: live (dpred pointer changes)
-        dzd = plan.buf("g.dzd", (T1, self.det_np))
-        if dpred is None:                            # SR-only loss
-            ops.zero_(dzd)
-        else:
-            ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
+        if plan.unit("detect").runs_bwd:
+            dzd = plan.buf("g.dzd", (T1, self.det_np))
+            if dpred is None:                            # SR-only loss
+                ops.zero_(dzd)
+            else:
+                ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
         if self.sr:
             self._sr_backward(plan, dsr)             # live too: its input gradients land in plan.sr's buffers
         overlap = False
@@ -1166,12 +1310,16 @@ class Engine:
             ops.replay(plan.bwd_main, probes=self.probes_bwd, start=pos)
         else:
             self._replay(plan, "bwd_main", plan.bwd_main, self.probes_bwd)
-        self._frontend_bwd(plan, P, x_rgb, x_ir)
+        if plan.unit("frontend").runs_bwd:
+            self._frontend_bwd(plan, P, x_rgb, x_ir)
+            if fz is not None:
+                for lo, hi in fz.dirty_runs(0, self.fe_end):             # its frozen parameters: the one launch wrote all sixteen
+                    ops.zero_(self.flat_grad[lo:hi])
         if self.ddp is not None:
             if overlap:
-                self.ddp.finish(self.flat_grad[:self.ddp_split])
+                self.ddp.finish(self.flat_grad[min(first, plan.bwd_marks[-1][1]): plan.bwd_marks[-1][1]])
             else:
-                self.ddp.reduce(self.flat_grad)
+                self.ddp.reduce(self.flat_grad[first:])
 
     def replay_encoder_backward(self, plan: Plan, x_rgb, x_ir):
         """Diagnostic / test hook: re-run the ENCODER part of the recorded backward (necks, stages 3..1, PatchMergings, patch
@@ -1179,8 +1327,12 @@ class Engine:
         gradient buffer.  The encoder has no cross-image coupling (LayerNorm, windows, per-image shifts), so a batch's encoder
         gradients are the sum of its images' - tests/test_fullsize_gpu.py checks the B = 8 training step that way.  Needs one
         ordinary backward on this plan first (it records the launches) and the activations of the latest forward."""
-        if plan.bwd_main is None or plan.enc_bwd_start is None:
+        if plan.bwd_main is None:
             raise RuntimeError("replay_encoder_backward: run one backward on this plan first")
+        if plan.enc_bwd_start is None:
+            off = [u.name for u in plan.fz.units.values() if not u.runs_bwd] if plan.fz is not None else []
+            raise RuntimeError("replay_encoder_backward: the encoder's backward was not recorded on this plan: frozen parameters "
+                               f"(requires_grad False) leave no backward for {', '.join(off[:4])}{' ...' if len(off) > 4 else ''}")
         ops.replay(plan.bwd_main, start=plan.enc_bwd_start)
         self._frontend_bwd(plan, self._prep_for(plan.dt), x_rgb, x_ir)
 
@@ -1201,48 +1353,77 @@ class Engine:
             ops.cross_attn_ln_bwd(plan.bufs["fe.e"], fe["g"], plan.bufs["g.dx0"], de, self.g_fe_g, self.g_fe_be, B, S, ca_ws, ca_shift)
             ops.patch_embed4_bwd(x_rgb, x_ir, x_ir.shape[1] * S * S, de, self.g_fe_w, self.g_fe_b, B, S)
 
+    def _zero_frozen(self, plan: Plan, lo, hi):
+        """Frozen parameters' slices in [lo, hi) of the flat buffer that a launch fusing dX with parameter gradients may have
+        written (LayerNorm, BatchNorm, attention backwards; a GEMM whose weight is trainable and whose bias is not): back to zero,
+        one memset per contiguous run (freeze.FreezeRecord.dirty_runs).  Nothing frozen: no launch."""
+        if plan.fz is not None:
+            for a, b_ in plan.fz.dirty_runs(lo, hi):
+                ops.zero_(self.flat_grad[a:b_])
+
+    def _mark(self, plan: Plan, lo, hi):
+        """the gradients in [lo, hi) are final at this point of the recorded list: a data-parallel bucket (the buffer's frozen head
+        is zero on every rank and is left out)"""
+        self._zero_frozen(plan, lo, hi)
+        lo = max(lo, 0 if plan.fz is None else plan.fz.first_trainable_offset)
+        if lo < hi:
+            plan.bwd_marks.append((ops.recorded_count(), lo, hi))
+
     def _backward_main(self, plan: Plan, P):
         B, S = plan.B, plan.S
         t = S // 4
         wT, g, b = P["wT"], self.g, plan.bufs
         enc = self.model.image_encoder
+        U, T = plan.unit, plan.trainable
         ops.zero_(plan.zpool("b"))                   # BN-backward reduction accumulators of every head conv
         T1, T2, T3 = B * t * t, B * (t // 2) ** 2, B * (t // 4) ** 2
         h2, h4 = t // 2, t // 4
         # ---- Detect
-        dzd = b["g.dzd"]
         hu = self.head.by_row[self.head.head_out[0]]
         cd = self.head.head_out[1]
-        ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np, lddw=cd,
-                    dbias=g[self.det_name + "m.0.bias"])
-        dyd = plan.buf("g.dyd", (T1, cd))
-        ops.gemm_nt([SegSpec(dzd)], wT[self.det_name + "m.0.weight"], dyd, T1, cd, self.det_np)
+        gout = {}                                                    # headgraph.Ref -> (buffer, ld, column offset)
+        if U("detect").runs_bwd:
+            dzd = b["g.dzd"]
+            if U("detect").any_wgrad:
+                ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np,
+                            lddw=cd, dbias=g[self.det_name + "m.0.bias"])
+            if U("detect").any_dx:
+                dyd = plan.buf("g.dyd", (T1, cd))
+                ops.gemm_nt([SegSpec(dzd)], wT[self.det_name + "m.0.weight"], dyd, T1, cd, self.det_np)
+                gout[hu.ref] = (dyd, cd, 0)
         # ---- head units in reverse: every unit returns d(its concatenated input) [M][c1]; the gradient of an Upsample /
-        #      Concat input is a column slice of it (nearest x2^shr upsample: summed over the 2^shr x 2^shr children)
-        gout = {hu.ref: (dyd, cd, 0)}                                # headgraph.Ref -> (buffer, ld, column offset)
-        extra = self._sr_extra(plan) if self.sr else {}
+        #      Concat input is a column slice of it (nearest x2^shr upsample: summed over the 2^shr x 2^shr children).  A unit
+        #      whose output needs no gradient is passed over; an input that needs none gets no slice (and no gather_sum_rows)
+        extra = self._sr_extra(plan) if self.sr and U("model_up").runs_bwd and U("model_up").any_dx else {}
         for u in reversed(self.head.units):
             H = t >> u.level
             M = B * H * H
             tag = f"h{u.k}"
+            ur = U(tag)
+            if not ur.runs_bwd:
+                continue
             dy, ld, off = gout.pop(u.ref)
             self._add_extra(plan, extra, u.ref, (dy, ld, off))
             if u.kind == "Conv":
                 dz = self._conv_bwd(plan, tag, dy, ld, off)
-                din = plan.buf(tag + ".din", (M, u.c1))
-                w_ = wT[f"detect.{u.k}.conv.weight"]
-                if u.ksize == 1:
-                    ops.gemm_nt([SegSpec(dz)], w_, din, M, u.c1, u.c2)
-                else:
-                    segs = [SegSpec(dz, u.c2, 0, -dy_, -dx_, 1, 0, H, H) for (dy_, dx_) in TAPS3]
-                    ops.gemm_nt(segs, w_, din, M, u.c1, 9 * u.c2, spatial=(H, H))
+                din = None
+                if ur.any_dx:
+                    din = plan.buf(tag + ".din", (M, u.c1))
+                    w_ = wT[f"detect.{u.k}.conv.weight"]
+                    if u.ksize == 1:
+                        ops.gemm_nt([SegSpec(dz)], w_, din, M, u.c1, u.c2)
+                    else:
+                        segs = [SegSpec(dz, u.c2, 0, -dy_, -dx_, 1, 0, H, H) for (dy_, dx_) in TAPS3]
+                        ops.gemm_nt(segs, w_, din, M, u.c1, 9 * u.c2, spatial=(H, H))
             elif u.kind == "C3":
                 din = self._c3_bwd(plan, P, tag, dy, ld, off)
             else:
                 din = self._spp_bwd(plan, P, tag, dy, ld, off)
             coff = 0
-            for ref, c, shr in u.parts:
-                if shr == 0:
+            for (ref, c, shr), src in zip(u.parts, self.unit_inputs[tag]):
+                if not ur.needs_dx[src]:
+                    pass
+                elif shr == 0:
                     gout[ref] = (din, u.c1, coff)
                 else:
                     Hs = H >> shr
@@ -1251,49 +1432,71 @@ class Engine:
                     gout[ref] = (dsrc, c, 0)
                 coff += c
         for j in range(3):
-            self._add_extra(plan, extra, Ref("enc", j), gout[Ref("enc", j)])
-        (gf0, ld0, off0), (gf1, ld1, off1), (gf2, ld2, off2) = (gout[Ref("enc", j)] for j in range(3))
+            if Ref("enc", j) in gout:
+                self._add_extra(plan, extra, Ref("enc", j), gout[Ref("enc", j)])
+        (gf0, ld0, off0), (gf1, ld1, off1), (gf2, ld2, off2) = (gout.get(Ref("enc", j), (None, 0, 0)) for j in range(3))
         # where the head's backward ends and the encoder's begins, and the buffers the head left d(f0), d(f1), d(f2) in
         # (token-major rows, `ld` columns, the feature's columns at `off`): replay_encoder_backward re-runs the rest from there
-        plan.enc_bwd_start = ops.recorded_count()
-        plan.enc_gin = [(gf0, ld0, off0, 256), (gf1, ld1, off1, 256), (gf2, ld2, off2, 512)]
+        # (a trainable front end: every unit above it has a backward, the encoder's is recorded whole)
+        if U("frontend").runs_bwd:
+            plan.enc_bwd_start = ops.recorded_count()
+            plan.enc_gin = [(gf0, ld0, off0, 256), (gf1, ld1, off1, 256), (gf2, ld2, off2, 512)]
         # ---- neck3 + stage 3
-        s3out = b["stage3.0.xo"]
-        d3a = plan.buf("g.dA.768", (T3, 768))
-        d3b = plan.buf("g.dB.768", (T3, 768))
-        self._linear_bwd(P, E + "neck3", gf2, s3out, d3a, T3, 512, 768, bias=False, ldy=ld2, y_off=off2)
-        self._block_bwd(plan, P, "stage3.0", enc.stage3[0], d3a, d3b)
+        d3a = d3b = None
+        if U("neck3").runs_bwd:
+            s3out = b["stage3.0.xo"]
+            d3a = plan.buf("g.dA.768", (T3, 768))
+            d3b = plan.buf("g.dB.768", (T3, 768))
+            self._linear_bwd(P, E + "neck3", gf2, s3out, d3a, T3, 512, 768, bias=False, ldy=ld2, y_off=off2, plan=plan,
+                             need_dx=U("neck3").any_dx)
+            self._block_bwd(plan, P, "stage3.0", enc.stage3[0], d3a, d3b)
         # head, neck 3 and stage 3 gradients are final: first data-parallel bucket (ddp.GradReducer.reduce_async)
-        plan.bwd_marks.append((ops.recorded_count(), self.ddp_split3, self.flat_grad.numel()))
+        self._mark(plan, self.ddp_split3, self.flat_grad.numel())
         # ---- pmerging2 -> d(stage2 out) ; + neck2
-        dA = plan.buf("g.dA.384", (T2, 384))
-        dB = plan.buf("g.dB.384", (T2, 384))
-        self._merge_bwd(plan, P, "pmerging2", d3b, dA)
-        s2out = b["stage2.3.xo"]
-        self._linear_bwd(P, E + "neck2", gf1, s2out, dA, T2, 256, 384, bias=False, ldy=ld1, y_off=off1, resid=dA)
-        cur, other = dA, dB
-        for i in reversed(range(4)):
-            self._block_bwd(plan, P, f"stage2.{i}", enc.stage2[i], cur, other)
-            cur, other = other, cur
+        cur = None
+        if U("neck2").runs_bwd or U("pmerging2").runs_bwd:
+            dA = plan.buf("g.dA.384", (T2, 384))
+            dB = plan.buf("g.dB.384", (T2, 384))
+            if U("pmerging2").runs_bwd:
+                self._merge_bwd(plan, P, "pmerging2", d3b, dA)
+            s2out = b["stage2.3.xo"]
+            # (the neck and the PatchMerging read the same tensor: both leave an input gradient or neither does)
+            if U("neck2").runs_bwd:
+                self._linear_bwd(P, E + "neck2", gf1, s2out, dA, T2, 256, 384, bias=False, ldy=ld1, y_off=off1, resid=dA, plan=plan,
+                                 need_dx=U("neck2").any_dx)
+            cur, other = dA, dB
+            for i in reversed(range(4)):
+                self._block_bwd(plan, P, f"stage2.{i}", enc.stage2[i], cur, other)
+                cur, other = other, cur
         # ---- pmerging1 -> d(stage1 out5) ; + neck1
-        dA = plan.buf("g.dA.192", (T1, 192))
-        dB = plan.buf("g.dB.192", (T1, 192))
-        self._merge_bwd(plan, P, "pmerging1", cur, dA)
-        o4, o5 = b["stage1.4.xo"], b["stage1.5.xo"]
-        ops.gemm_tn(gf0, [SegSpec(o4), SegSpec(o5)], g[E + "neck1.weight"], T1, 256, 384, ldy=ld0, y_off=off0)
-        df0 = SegSpec(gf0, 256, off0)
-        ops.gemm_nt([df0], wT[E + "neck1.weight"], dA, T1, 192, 256, w_off=192 * 256, resid=dA)        # d out5 += df0 @ Wn1[:,192:]
+        n1 = U("neck1").runs_bwd
+        if n1 or U("pmerging1").runs_bwd:
+            dA = plan.buf("g.dA.192", (T1, 192))
+            dB = plan.buf("g.dB.192", (T1, 192))
+            if U("pmerging1").runs_bwd:
+                self._merge_bwd(plan, P, "pmerging1", cur, dA)
+        if n1:
+            o4, o5 = b["stage1.4.xo"], b["stage1.5.xo"]
+            if T(E + "neck1.weight"):
+                ops.gemm_tn(gf0, [SegSpec(o4), SegSpec(o5)], g[E + "neck1.weight"], T1, 256, 384, ldy=ld0, y_off=off0)
+            df0 = SegSpec(gf0, 256, off0)
+            if U("neck1").needs_dx["stage1.5.mlp"]:          # (then PatchMerging 1 has left its input gradient in dA)
+                ops.gemm_nt([df0], wT[E + "neck1.weight"], dA, T1, 192, 256, w_off=192 * 256, resid=dA)        # d out5 += df0 @ Wn1[:,192:]
         # every gradient from PatchMerging 1 to the end of the flat buffer is final here: data-parallel runs start
         # their all-reduce now, under the stage-1 backward (ddp.GradReducer.reduce_async)
-        plan.bwd_marks.append((ops.recorded_count(), self.ddp_split, self.ddp_split3))
-        self._block_bwd(plan, P, "stage1.5", enc.stage1[5], dA, dB)
-        ops.gemm_nt([df0], wT[E + "neck1.weight"], dB, T1, 192, 256, resid=dB)                           # d out4 += df0 @ Wn1[:,:192]
-        cur, other = dB, dA
-        for i in reversed(range(5)):
-            self._block_bwd(plan, P, f"stage1.{i}", enc.stage1[i], cur, other)
-            cur, other = other, cur
-        # ---- patch_embed 1x1 + pos_embed
-        if plan.saved["use_pos"]:
-            ops.batch_sum(cur, g[E + "pos_embed"], B, t * t * 192)
-        dx0 = plan.buf("g.dx0", (T1, 192))
-        self._linear_bwd(P, E + "patch_embed.proj", cur, b["x0"], dx0, T1, 192, 192)
+        self._mark(plan, self.ddp_split, self.ddp_split3)
+        if U("stage1.5.mlp").runs_bwd:
+            self._block_bwd(plan, P, "stage1.5", enc.stage1[5], dA, dB)
+            if n1 and U("neck1").needs_dx["stage1.4.mlp"]:
+                ops.gemm_nt([df0], wT[E + "neck1.weight"], dB, T1, 192, 256, resid=dB)                       # d out4 += df0 @ Wn1[:,:192]
+            cur, other = dB, dA
+            for i in reversed(range(5)):
+                self._block_bwd(plan, P, f"stage1.{i}", enc.stage1[i], cur, other)
+                cur, other = other, cur
+            # ---- patch_embed 1x1 + pos_embed
+            if U("embed").runs_bwd:
+                if plan.saved["use_pos"] and T(E + "pos_embed"):
+                    ops.batch_sum(cur, g[E + "pos_embed"], B, t * t * 192)
+                dx0 = plan.buf("g.dx0", (T1, 192)) if U("embed").any_dx else None
+                self._linear_bwd(P, E + "patch_embed.proj", cur, b["x0"], dx0, T1, 192, 192, plan=plan, need_dx=U("embed").any_dx)
+        self._zero_frozen(plan, self.fe_end, self.ddp_split)

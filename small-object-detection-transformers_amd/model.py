@@ -313,6 +313,17 @@ def parse_model(d: dict, string: str, ch: List[int]):
     return nn.Sequential(*layers), sorted(save)
 
 
+class FreezeSummary(list):
+    """Model.freeze_summary(): rows (unit, runs_bwd, saves, trainable parameters, frozen parameters); prints as a table."""
+
+    def __str__(self):
+        lines = [f"{'unit':<16}{'backward':>9}{'saves':>7}{'trainable':>11}{'frozen':>8}"]
+        lines += [f"{name:<16}{'yes' if runs else '-':>9}{'yes' if saves else '-':>7}{nt:>11}{nf:>8}" for name, runs, saves, nt, nf in self]
+        runs = sum(1 for r in self if r[1])
+        lines.append(f"{runs} of {len(self)} units run a backward; {sum(r[3] for r in self)} trainable / {sum(r[4] for r in self)} frozen tensors")
+        return "\n".join(lines)
+
+
 class NMS(nn.Module):
     """common.py:285-295: non_max_suppression as a module (thresholds are class attributes, as in the reference)."""
     conf = 0.25
@@ -422,6 +433,23 @@ class Model(nn.Module):
         n_p = sum(x.numel() for x in self.parameters())
         n_g = sum(x.numel() for x in self.parameters() if x.requires_grad)
         print(f"Model Summary: {len(list(self.modules()))} layers, {n_p} parameters, {n_g} gradients")
+
+    def freeze_record(self):
+        """freeze.FreezeRecord for the requires_grad flags as they are now (Train.py:115-121 sets them from its `freeze` list):
+        per unit of the engine, whether its backward runs, which inputs get a gradient, which parameters do, whether its forward
+        saves for the backward.  Host code only: no device, no engine."""
+        from . import freeze
+        from .headgraph import parse_head
+        named = dict(self.named_parameters())
+        order, offs, size = freeze.grad_layout({n: p.numel() for n, p in named.items()})
+        graph = freeze.unit_graph(list(named), parse_head(self), self.sr)
+        return freeze.propagate(graph, [n for n, p in named.items() if not p.requires_grad], order, offs, size)
+
+    def freeze_summary(self):
+        """What the current requires_grad flags bought, unit by unit in forward order: a list of (unit, runs_bwd, saves, trainable
+        parameters, frozen parameters) rows whose str() is the table.  A unit with runs_bwd False costs no backward launch and
+        its forward keeps nothing for one."""
+        return FreezeSummary(self.freeze_record().summary())
 
     def __deepcopy__(self, memo):               # ModelEMA (torch_utils.py:283): copy parameters, not the engine
         cls = self.__class__

@@ -125,8 +125,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
         eng = self.model._get_engine()
         if eng is not self._eng:
             self._eng, self._state, self._sig = eng, [torch.zeros_like(eng.flat_param) for _ in range(self._n_state)], None
-        sig = tuple(tuple(id(p) for p in g["params"]) for g in self.param_groups)
-        if sig != self._sig:       # chunk -> group map (255: padding / parameters this optimizer does not own)
+        # (the requires_grad bits are part of the signature: a parameter frozen after the optimizer was built - Train.py:328-333 -
+        #  has no gradient, and torch's optimizers pass over a parameter whose .grad is None: no decay, no momentum, no moment update)
+        sig = tuple(tuple((id(p), p.requires_grad) for p in g["params"]) for g in self.param_groups)
+        if sig != self._sig:       # chunk -> group map (255: padding / frozen parameters / parameters this optimizer does not own)
             gmap = torch.full((eng.flat_param.numel() // 4,), 255, dtype=torch.uint8)
             off_of = {id(eng.params[n]): (eng.grad_offsets[n], eng.params[n].numel()) for n in eng.grad_order}
             for gi, g in enumerate(self.param_groups):
@@ -134,7 +136,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
                     if id(p) not in off_of:
                         raise ValueError(f"{type(self).__name__}: a parameter does not belong to the model's engine")
                     o, n = off_of[id(p)]
-                    gmap[o // 4: (o + n + 3) // 4] = gi
+                    gmap[o // 4: (o + n + 3) // 4] = gi if p.requires_grad else 255
             self._groups, self._sig = gmap.to(eng.dev), sig
         return eng
 

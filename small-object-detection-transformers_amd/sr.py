@@ -144,6 +144,11 @@ class SRBranch:
             self.c[c.name] = c
         self._tab = tab.upload(self.dev)
         self.bufs: Dict[str, torch.Tensor] = {}
+        # backward switches (the engine sets them from the requires_grad flags before every backward): trainable(*names) -> whether
+        # any of these parameters takes a gradient (a convolution whose weight and bias are frozen gets no weight-gradient launch);
+        # need_dx False: the branch's two inputs need no gradient, the two entry convolutions compute none
+        self.trainable = lambda *names: True
+        self.need_dx = True
         self.prepare()
 
     def prepare(self):
@@ -205,12 +210,16 @@ class SRBranch:
         return (out.dtype == torch.bfloat16 and c.k == 3 and c.cin == 64 and c.cout == 64 and ldc is None and out.shape[-1] == 64
                 and s0.ld == 64 and s0.klen == 64 and s0.coff == 0 and s0.shr == 0 and s0.mul == 1)
 
+    def _wg(self, name):
+        return self.trainable(name + ".weight", *([name + ".bias"] if self.c[name].bias is not None else []))
+
     def _conv_bwd(self, name, dy, lddy, fwd, H, W, M, dx, *, dx_n=None, w_row0=0, drelu_aux=None, aux_off=0, resid=None, wgrad=True):
         """Weight / bias gradients of conv `name` (+= into self.g) and, when dx is given,
         dx = conv^T(dy) for input channels [w_row0, w_row0 + dx_n), masked by drelu_aux > 0, + resid.
         dy: [M][lddy] with the gradient in the first Cout columns and zeros up to Np."""
         c = self.c[name]
         segs, sp = fwd
+        wgrad = wgrad and self._wg(name)
         if c.k == 3 and lddy == 64 and self._direct64(c, segs[4], dy) and dx_n is None and w_row0 == 0 and aux_off == 0:
             B = M // (H * W)
             if wgrad:
@@ -300,8 +309,8 @@ class SRBranch:
         ops.bilinear_up2_bwd(dcu, dxr, B, h, w, cx, relu_out=b["xr"])
         d_low = self._buf("g.low", (M1, c[d + "conv1"].cin))
         d_x = self._buf("g.x", (Mh, c[d + "conv2"].cin))
-        self._conv_bwd(d + "conv1", da, ca, self.f_c1, H, W, M1, d_low)
-        self._conv_bwd(d + "conv2", dxr, cx, self.f_c2, h, w, Mh, d_x)
+        self._conv_bwd(d + "conv1", da, ca, self.f_c1, H, W, M1, d_low if self.need_dx else None)
+        self._conv_bwd(d + "conv2", dxr, cx, self.f_c2, h, w, Mh, d_x if self.need_dx else None)
         return d_low, d_x
 
     # ------------------------------------------------------------------ EDSR (edsr.py:55-102)
@@ -367,9 +376,10 @@ class SRBranch:
         if self.f_o[0] == "direct":
             # ... and its gradients read the float32 (B, ch, 8H, 8W) gradient in place
             name = e + "tail.1"
-            scr = self._buf("c3.scratch", (ops.conv3_n8_wgrad_scratch_floats(),), torch.float32)
-            ops.conv3_n8_wgrad(None, self.f_o[1], self.g[name + ".weight"], self.g[name + ".bias"] if ct.bias is not None else None, scr,
-                               B, gh, gw, ct.cout, dy_nchw=dy)
+            if self._wg(name):
+                scr = self._buf("c3.scratch", (ops.conv3_n8_wgrad_scratch_floats(),), torch.float32)
+                ops.conv3_n8_wgrad(None, self.f_o[1], self.g[name + ".weight"], self.g[name + ".bias"] if ct.bias is not None else None, scr,
+                                   B, gh, gw, ct.cout, dy_nchw=dy)
             ops.conv3_n8_dgrad(None, ct.wT, dcur, B, gh, gw, dy_nchw=dy, cout=ct.cout)
         else:
             do = self._buf("g.o", (B * gh * gw, ct.np_))
@@ -384,8 +394,9 @@ class SRBranch:
                 name, cj = f"{e}tail.0.{2 * j}", c[f"{e}tail.0.{2 * j}"]
                 scr = self._buf("c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
                 for pl in range(4):
-                    ops.conv3_c64_wgrad(dcur, fj[1], self.g[name + ".weight"], self.g[name + ".bias"], scr, B, hj, wj,
-                                        geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
+                    if self._wg(name):
+                        ops.conv3_c64_wgrad(dcur, fj[1], self.g[name + ".weight"], self.g[name + ".bias"], scr, B, hj, wj,
+                                            geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
                     ops.conv3_c64_fwd(dcur, cj.wTp[pl], dsrc, B, hj, wj, flip=True, resid=dsrc if pl else None,
                                       geo=ops.conv3_geo(inp=(2, pl >> 1, pl & 1)))
             else:
