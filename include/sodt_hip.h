@@ -396,13 +396,14 @@ int sodt_bn_affine(const float* mean_rstd, const float* gamma, const float* beta
    chunk of the row for the whole launch.  Wider rows return SODT_EINVAL. */
 int sodt_bn_silu_fwd(const void* z, const float* mean_rstd, const float* gamma, const float* beta,
                      void* y, int ldy, long M, int C, int dtype, sodt_stream_t st);
-/* pass 1: red[0][c] += sum g, red[1][c] += sum g*xhat with g = dy * silu'(a);  pass 2: dz */
+/* pass 1: red[0][c] += sum g, red[1][c] += sum g*xhat with g = dy * silu'(a);  pass 2: dz, rows lddz elements apart (dense: C;
+   a column slice of a wider buffer: the pointer carries the column offset, as dy's does) */
 int sodt_bn_silu_bwd_reduce(const void* dy, int lddy, const void* z, const float* mean_rstd,
                             const float* gamma, const float* beta, double* red, long M, int C,
                             int dtype, sodt_stream_t st);
 int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, const float* mean_rstd,
                            const float* gamma, const float* beta, const double* red, void* dz,
-                           float* dgamma, float* dbeta, long M, int C, int dtype, sodt_stream_t st);
+                           float* dgamma, float* dbeta, long M, int C, int lddz, int dtype, sodt_stream_t st);
 
 /* dst[(b,y,x)][coff : coff+C] = src[(b, y>>shr, x>>shr)][0:C]  (nn.Upsample nearest + Concat slot) */
 int sodt_copy_rows(const void* src, int lds_, void* dst, int ldd, int B, int Ho, int Wo, int shr, int C,
@@ -427,6 +428,37 @@ int sodt_detect_unpermute(const float* dpred, void* dz, int ldz, int B, int HW, 
 /* Detect eval decode (model.py:61-64): raw f32 (B,na,ny,nx,no) -> z f32 (B, na*ny*nx, no) */
 int sodt_detect_decode(const float* raw, const float* anchor_grid, float* z, int B, int na, int ny, int nx,
                        int no, float stride, sodt_stream_t st);
+
+/* The Detect level in one pass each way (csrc/detect.hip; model.py:44-58 and its autograd), bf16 only.  M = B * HW rows, N = na * no:
+ *   sodt_detect_fwd   pred[b][a][p][o] (f32) = X[b*HW + p][0:K] . W[a*no + o][0:K] + bias[a*no + o]  - what sodt_gemm_nt computes
+ *                     with SODT_EPI_DETECT | SODT_EPI_BIAS (same products, same K order), written as whole runs of pred
+ *   sodt_detect_bwd   dZ[m][n] = bf16(pred[b][a][p][o]) (pred holds d(pred) here; the rounding of sodt_detect_unpermute), then
+ *                     dX[M][K] (bf16) = dZ @ W;  dW[N][K] (f32) += dZ^T @ X;  dbias[N] (f32) += column sums of dZ (NULL: skipped)
+ *                     flags: SODT_DETECT_NO_WGRAD leaves dW / dbias alone, SODT_DETECT_NO_DX leaves dX alone (not both).
+ *                     With dW the caller gives a scratch of >= splits * (48 K + 48) floats: every slice leaves its partial there
+ *                     and a second kernel adds the live slices to dW / dbias in a fixed order (run-to-run deterministic; equal
+ *                     to sodt_gemm_tn's result up to f32 summation order).
+ * X, W, dX: row-major bf16, 16-byte aligned, leading dimensions multiples of 8 and >= K; pred, bias, dW, dbias, partial 16-byte
+ * aligned, lddw a multiple of 4 and >= K.  splits: M is cut into this many slices of whole 32-row stages, one workgroup each.
+ * K not a multiple of 32 or beyond 256, na * no > 48, float32, an alignment off, a scratch too small: SODT_EINVAL, nothing
+ * launched or written (callers run sodt_gemm_nt / sodt_detect_unpermute + sodt_gemm_tn + sodt_gemm_nt). */
+#define SODT_DETECT_NO_WGRAD 1
+#define SODT_DETECT_NO_DX 2
+typedef struct {
+  const void* X; int ldx;
+  const void* W; int ldw;
+  const float* bias;
+  float* pred;
+  void* dX; int lddx;
+  float* dW; int lddw;
+  float* dbias;
+  int B, HW, na, no, K, flags;
+  int splits;
+  float* partial;
+  long partial_floats;
+} sodt_detect_args;
+int sodt_detect_fwd(const sodt_detect_args* g, int dtype, sodt_stream_t st);
+int sodt_detect_bwd(const sodt_detect_args* g, int dtype, sodt_stream_t st);
 
 /* ---- non_max_suppression (general.py:425-512), one image per call, eval only ---------------------------
  * z: decoded rows (N, 5+nc) f32 [cx cy w h obj cls...] of one image (Detect eval output, model.py:64).

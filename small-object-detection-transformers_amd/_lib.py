@@ -30,6 +30,7 @@ SR_MODES = {"IR": 0, "RGB": 1, "RGB+IR": 2}           # SODT_SR_IR / SODT_SR_RGB
 EPI_BIAS, EPI_RESID, EPI_GELU_DUAL, EPI_DGELU = 1, 2, 4, 8
 EPI_STATS, EPI_AFFINE_SILU, EPI_DETECT, EPI_OUT_F32 = 16, 32, 64, 128
 EPI_GELU, EPI_DGELU_RC, EPI_RELU, EPI_DRELU = 256, 512, 2048, 4096      # (1024: retired, see include/sodt_hip.h)
+DETECT_NO_WGRAD, DETECT_NO_DX = 1, 2                  # SODT_DETECT_NO_WGRAD / SODT_DETECT_NO_DX
 STATS_REPL = 16      # SODT_STATS_REPL: replicas of the [2][N] f64 BatchNorm statistics buffer
 
 
@@ -78,6 +79,20 @@ class LinBwdArgs(C.Structure):
                 ("dW", C.c_void_p), ("lddw", C.c_int),
                 ("dbias", C.c_void_p),
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("flags", C.c_int),
+                ("splits", C.c_int),
+                ("partial", C.c_void_p), ("partial_floats", C.c_long)]
+
+
+class DetectArgs(C.Structure):
+    """sodt_detect_args (include/sodt_hip.h): the Detect level, forward or backward, in one pass."""
+    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int),
+                ("W", C.c_void_p), ("ldw", C.c_int),
+                ("bias", C.c_void_p),
+                ("pred", C.c_void_p),
+                ("dX", C.c_void_p), ("lddx", C.c_int),
+                ("dW", C.c_void_p), ("lddw", C.c_int),
+                ("dbias", C.c_void_p),
+                ("B", C.c_int), ("HW", C.c_int), ("na", C.c_int), ("no", C.c_int), ("K", C.c_int), ("flags", C.c_int),
                 ("splits", C.c_int),
                 ("partial", C.c_void_p), ("partial_floats", C.c_long)]
 
@@ -142,11 +157,13 @@ SIGNATURES = {
     "sodt_bn_affine": [_P, _P, _P, _P, _P, _I, _P],
     "sodt_bn_silu_fwd": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
     "sodt_bn_silu_bwd_reduce": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _I, _P],
-    "sodt_bn_silu_bwd_apply": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
+    "sodt_bn_silu_bwd_apply": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "sodt_copy_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_gather_sum_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_detect_unpermute": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_detect_decode": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "sodt_detect_fwd": [C.POINTER(DetectArgs), _I, _P],
+    "sodt_detect_bwd": [C.POINTER(DetectArgs), _I, _P],
     "sodt_prep_weights": [_P, _I, _I, _I, _P],
     "sodt_transpose_f32": [_P, _P, _I, _I, _I, _P],
     "sodt_cast": [_P, _P, _L, _I, _I, _P],

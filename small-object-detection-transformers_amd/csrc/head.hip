@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restr
                                                                const float* __restrict__ mr, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const double* __restrict__ red,
                                                                T* __restrict__ dz, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta, long M, int C) {
+                                                               float* __restrict__ dbeta, long M, int C, int lddz) {
   constexpr int KPL = TT<T>::KPL;
   constexpr int U = BN_APP_ROWS;
   const int CH = C / KPL;
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restr
         const float xh = (v[j] - mu[j]) * rs[j];
         o[j] = bn_dz<T>(d[j], xh, __builtin_fmaf(xh, ga[j], be[j]), gr[j], mg[j], mgx[j]);
       }
-      if (mm < M) *(uint4*)(dz + mm * C + c0) = pack<T>(o);
+      if (mm < M) *(uint4*)(dz + mm * lddz + c0) = pack<T>(o);
     }
   }
 }
@@ -500,12 +500,13 @@ extern "C" int sodt_col_stats(const void* z, int ldz, double* stats, long M, int
 
 extern "C" int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, const float* mean_rstd,
                                       const float* gamma, const float* beta, const double* red, void* dz,
-                                      float* dgamma, float* dbeta, long M, int C, int dtype, sodt_stream_t st) {
+                                      float* dgamma, float* dbeta, long M, int C, int lddz, int dtype, sodt_stream_t st) {
   const int kpl = dtype == SODT_BF16 ? 8 : 4;
   if (!dy || !z || !red || !dz || !dgamma || !dbeta || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
+  if (lddz < C || (lddz % kpl)) return SODT_EINVAL;
   const unsigned gr = bn_grid(M, C / kpl, BN_APP_ROWS, BN_APP_GRID);
-  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C);
-  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C);
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C, lddz);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C, lddz);
   return SODT_EINVAL;
 }
 

@@ -62,6 +62,7 @@ class Plan:
         self.sr = None                            # this plan's sr.SRBranch (Engine._sr_forward)
         self.enc_bwd_start: Optional[int] = None  # index in bwd_main where the head's backward ends and the encoder's begins
         self.enc_gin: Optional[list] = None       # [(buf, ld, off, c)]: where the head leaves d(f0), d(f1), d(f2)
+        self.det_fused: Optional[bool] = None     # Detect's backward is the live one-pass launch, not part of bwd_main (set with bwd_main)
 
     def unit(self, name):
         """the freeze.UnitRecord of unit `name`"""
@@ -275,6 +276,11 @@ class Engine:
         # bf16, C = 192: backward of attn.proj and of the conv-MLP's fc2 as ONE launch each (csrc/linbwd.hip: dX and dW from one read
         # of dY) against the sodt_gemm_tn + sodt_gemm_nt pair
         self.use_fused_linbwd = True
+        # bf16: the Detect level as one pass each way (csrc/detect.hip) against sodt_gemm_nt with the Detect epilogue and
+        # sodt_detect_unpermute + sodt_gemm_tn + sodt_gemm_nt; read when a plan's backward is first recorded and at every forward
+        self.use_fused_detect = True
+        # bf16: the stride-4 C3 forms d(input) of cv1 and cv2 in one GEMM over their concatenated dz (read when the weights are prepared)
+        self.use_merged_c3_din = True
         # 2x2-conv MLPs (bf16): fc1 folded into the convolution's weights (csrc/convmlp.hip) - no fc1 GEMM, and in the backward no
         # d(x) = du W1 and no dW1 GEMM; widths above this run the three-GEMM form (the composition kernels are plain f32 loops)
         self.convmlp_fold_maxc = 384
@@ -441,6 +447,19 @@ class Engine:
                 tab_t.add(p, w[n], (N, K, taps), (0, 2, 1), taps * K)
             wT[n] = torch.zeros(K, taps * Np, device=dev, dtype=dt)          # [K][tap*N + n]
             tab_t.add(p, wT[n], (N, K, taps), (1, 2, 0), taps * Np)
+        # C3 units whose cv1 / cv2 input gradient runs as one GEMM (_c3_bwd): [cv1.weight^T | cv2.weight^T], [c1][2 c_].  bf16 rows of
+        # at most 384 bytes only - the B-stationary kernel's range, the route the two separate launches take today
+        wT12: Dict[str, torch.Tensor] = {}
+        if dt == torch.bfloat16 and self.use_merged_c3_din:
+            for u in self.head.units:
+                if u.kind == "C3" and 2 * u.c2 <= 384 and u.c2 % 64 == 0:
+                    pn = f"detect.{u.k}."
+                    p1, p2 = self.params[pn + "cv1.conv.weight"], self.params[pn + "cv2.conv.weight"]
+                    c_, c1 = p1.shape[0], p1.shape[1]
+                    w12 = torch.zeros(c1, 2 * c_, device=dev, dtype=dt)
+                    tab_t.add(p1, w12, (c_, c1, 1), (1, 2, 0), 2 * c_)
+                    tab_t.add(p2, w12[:, c_:], (c_, c1, 1), (1, 2, 0), 2 * c_)
+                    wT12[pn] = w12
         # Linear MLPs on the bf16 path keep only the activation: the backward GEMM recomputes the pre-activation from
         # [fc1.weight | fc2.weight^T] ([4C][2C]) in its first K half (SODT_EPI_DGELU_RC)
         wcat: Dict[str, torch.Tensor] = {}
@@ -486,7 +505,7 @@ class Engine:
                 if nb > 0:
                     wmsa[E + f"{sname}.{i}."] = torch.zeros(nb // (2 if dt == torch.bfloat16 else 4), device=dev, dtype=dt)
 
-        P = dict(w=w, wT=wT, wcat=wcat, cmlp=cmlp, bias_t=bias_t, fe=fe, tab_t=tab_t.upload(dev), tab_f=tab_f.upload(dev), dt=dt,
+        P = dict(w=w, wT=wT, wT12=wT12, wcat=wcat, cmlp=cmlp, bias_t=bias_t, fe=fe, tab_t=tab_t.upload(dev), tab_f=tab_f.upload(dev), dt=dt,
                  ones={}, wmsa=wmsa)
         self.prep[dt] = P
         return P
@@ -611,8 +630,10 @@ class Engine:
         T1 = B * t * t
         pred = torch.empty(B, self.na, t, t, self.no, device=self.dev, dtype=torch.float32)
         hrow, hc = self.head.head_out
-        ops.gemm_nt([SegSpec(self._ref_buf(plan, Ref("unit", hrow)))], P["w"][self.det_name + "m.0.weight"], pred, T1, self.na * self.no,
-                    hc, bias=self.params[self.det_name + "m.0.bias"], detect=(self.na, self.no, t * t))
+        hx, wd, bd = self._ref_buf(plan, Ref("unit", hrow)), P["w"][self.det_name + "m.0.weight"], self.params[self.det_name + "m.0.bias"]
+        if not (self.use_fused_detect and ops.detect_fused_ok(hc, self.na, self.no, plan.dt)
+                and ops.detect_fwd(hx, wd, bd, pred, B, t * t, self.na, self.no, hc)):
+            ops.gemm_nt([SegSpec(hx)], wd, pred, T1, self.na * self.no, hc, bias=bd, detect=(self.na, self.no, t * t))
         return pred
 
     def _replay(self, plan: Plan, key: str, calls, probes):
@@ -1096,28 +1117,30 @@ class Engine:
         return (s0.klen == 64 and s0.ld == 64 and s0.coff == 0 and s0.shr == 0 and s0.mul == 1 and s0.dy == 0 and s0.dx == 0
                 and all(s_.t is s0.t for s_ in segs))
 
-    def _conv_bwd(self, plan, tag, dy, lddy, dy_off):
-        """BN+SiLU backward and the conv weight gradient; returns dz (gradient at the conv output)."""
+    def _conv_bwd(self, plan, tag, dy, lddy, dy_off, dz_out=None):
+        """BN+SiLU backward and the conv weight gradient; returns dz (gradient at the conv output).  dz_out = (buffer, ld, column
+        offset): dz is written as that column slice of a wider buffer (1x1 convolutions) and the buffer is returned."""
         ops.set_tag(tag + ".bwd")
         p, g, b = self.params, self.g, plan.bufs
         sv = plan.saved[tag]
         M, K, Cout, k, pname = sv.M, sv.K, sv.Cout, sv.k, sv.pname
         red = plan.zbuf("b", tag + ".red", (2, Cout), torch.float64)                          # zeroed with the pool (_backward_main)
-        dz = plan.buf(tag + ".dz", (M, Cout))
+        dz, lddz, dz_off = dz_out if dz_out is not None else (plan.buf(tag + ".dz", (M, Cout)), Cout, 0)
         ops.bn_silu_bwd_reduce(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, M, Cout,
                                dy_off=dy_off)
         ops.bn_silu_bwd_apply(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, dz,
-                              g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off)
+                              g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off, lddz=lddz, dz_off=dz_off)
         cin = K // (k * k)
         if not plan.trainable(pname + "conv.weight"):
             pass
         elif sv.direct:
+            assert dz_out is None
             H, W = sv.spatial
             scr = plan.buf("g.c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
             ops.conv3_c64_wgrad(dz, sv.segs[4].t, g[pname + "conv.weight"], None, scr, M // (H * W), H, W)
         else:
             ops.gemm_tn(dz, sv.segs, g[pname + "conv.weight"], M, Cout, K, spatial=sv.spatial,
-                        kperm=(cin, k * k) if k > 1 else None)
+                        kperm=(cin, k * k) if k > 1 else None, ldy=lddz, y_off=dz_off)
         return dz
 
     def _c3_fwd(self, plan, P, tag, pname, segs, spatial, M, c1, c2):
@@ -1143,8 +1166,12 @@ class Engine:
         dcat = plan.buf(tag + ".dcat", (M, 2 * c_))
         ops.gemm_nt([SegSpec(dz3)], wT[pname + "cv3.conv.weight"], dcat, M, 2 * c_, c2)
         din = plan.buf(tag + ".din", (M, c1)) if dx else None
-        dzb = self._conv_bwd(plan, tag + ".cv2", dcat, 2 * c_, c_)
-        if dx:
+        # cv1 and cv2 read the same input: with their dz as the two halves of ONE [M][2 c_] buffer, d(input) = dz1 W1 + dz2 W2 is a
+        # single GEMM against [W1^T | W2^T] (one write of din, one rounding) instead of a GEMM and a second one with a residual
+        w12 = P["wT12"].get(pname) if dx else None
+        dz12 = (plan.buf(tag + ".dz12", (M, 2 * c_)), 2 * c_) if w12 is not None else None
+        dzb = self._conv_bwd(plan, tag + ".cv2", dcat, 2 * c_, c_, dz_out=dz12 + (c_,) if dz12 else None)
+        if dx and w12 is None:
             ops.gemm_nt([SegSpec(dzb)], wT[pname + "cv2.conv.weight"], din, M, c1, c_)
         dza3 = self._conv_bwd(plan, tag + ".m2", dcat, 2 * c_, 0)
         da = plan.buf(tag + ".da", (M, c_))
@@ -1155,8 +1182,10 @@ class Engine:
             ops.gemm_nt(segs, wT[pname + "m.0.cv2.conv.weight"], da, M, c_, 9 * c_, spatial=(H, W))
         dza2 = self._conv_bwd(plan, tag + ".m1", da, c_, 0)
         ops.gemm_nt([SegSpec(dza2)], wT[pname + "m.0.cv1.conv.weight"], da, M, c_, c_)
-        dza1 = self._conv_bwd(plan, tag + ".cv1", da, c_, 0)
-        if dx:
+        dza1 = self._conv_bwd(plan, tag + ".cv1", da, c_, 0, dz_out=dz12 + (0,) if dz12 else None)
+        if w12 is not None:
+            ops.gemm_nt([SegSpec(dza1)], w12, din, M, c1, 2 * c_)
+        elif dx:
             ops.gemm_nt([SegSpec(dza1)], wT[pname + "cv1.conv.weight"], din, M, c1, c_, resid=din)
         return din
 
@@ -1286,12 +1315,35 @@ class Engine:
         if self.ddp is not None:
             self.ddp.begin_backward(self.flat_grad, fresh)
         # (1) Detect backward: live (dpred pointer changes)
-        if plan.unit("detect").runs_bwd:
-            dzd = plan.buf("g.dzd", (T1, self.det_np))
-            if dpred is None:                            # SR-only loss
-                ops.zero_(dzd)
+        ud = plan.unit("detect")
+        if ud.runs_bwd:
+            cd = self.head.head_out[1]
+            if plan.bwd_main is None:                    # decided once per plan: the recorded list holds Detect's GEMMs or it does not
+                plan.det_fused = bool(self.use_fused_detect and ops.detect_fused_ok(cd, self.na, self.no, plan.dt))
+            if plan.det_fused:
+                # dX, dW and dbias from one read of dpred (csrc/detect.hip); g.dzd, the [T1][48] copy of dpred, does not exist here
+                dyd = plan.buf("g.dyd", (T1, cd)) if ud.any_dx else None
+                if dpred is None:                        # SR-only loss: a zero gradient, nothing for the parameters
+                    if dyd is not None:
+                        ops.zero_(dyd)
+                elif ud.any_wgrad or dyd is not None:
+                    wg, wn, bn = ud.any_wgrad, self.det_name + "m.0.weight", self.det_name + "m.0.bias"
+                    hx = plan.bufs[self.head.by_row[self.head.head_out[0]].out_name]
+                    if not ops.detect_bwd(dpred, hx, P["w"][wn], dyd, self.g[wn] if wg else None, self.g[bn] if wg else None,
+                                          B, t * t, self.na, self.no, cd, lddw=cd):
+                        # refused (a dpred off its alignment): the three launches it replaces, live and with the same outputs
+                        dzd = plan.buf("g.dzd", (T1, self.det_np))
+                        ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
+                        if wg:
+                            ops.gemm_tn(dzd, [SegSpec(hx)], self.g[wn], T1, self.na * self.no, cd, ldy=self.det_np, lddw=cd, dbias=self.g[bn])
+                        if dyd is not None:
+                            ops.gemm_nt([SegSpec(dzd)], P["wT"][wn], dyd, T1, cd, self.det_np)
             else:
-                ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
+                dzd = plan.buf("g.dzd", (T1, self.det_np))
+                if dpred is None:                            # SR-only loss
+                    ops.zero_(dzd)
+                else:
+                    ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
         if self.sr:
             self._sr_backward(plan, dsr)             # live too: its input gradients land in plan.sr's buffers
         overlap = False
@@ -1382,7 +1434,10 @@ class Engine:
         hu = self.head.by_row[self.head.head_out[0]]
         cd = self.head.head_out[1]
         gout = {}                                                    # headgraph.Ref -> (buffer, ld, column offset)
-        if U("detect").runs_bwd:
+        if U("detect").runs_bwd and plan.det_fused:
+            if U("detect").any_dx:                                   # written by the live sodt_detect_bwd (_backward, step (1))
+                gout[hu.ref] = (b["g.dyd"], cd, 0)
+        elif U("detect").runs_bwd:
             dzd = b["g.dzd"]
             if U("detect").any_wgrad:
                 ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np,

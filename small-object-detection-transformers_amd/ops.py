@@ -524,9 +524,11 @@ def bn_silu_bwd_reduce(dy, lddy, z, mean_rstd, gamma, beta, red, M, Cc, dy_off=0
             _p(beta), _p(red), M, Cc, dt_code(z))
 
 
-def bn_silu_bwd_apply(dy, lddy, z, mean_rstd, gamma, beta, red, dz, dgamma, dbeta, M, Cc, dy_off=0):
+def bn_silu_bwd_apply(dy, lddy, z, mean_rstd, gamma, beta, red, dz, dgamma, dbeta, M, Cc, dy_off=0, lddz=None, dz_off=0):
+    """dz may be a column slice of a wider buffer: rows lddz elements apart, starting at column dz_off (dense: Cc, 0)."""
     _launch("sodt_bn_silu_bwd_apply", dy.data_ptr() + dy_off * dy.element_size(), lddy, _p(z), _p(mean_rstd), _p(gamma),
-            _p(beta), _p(red), _p(dz), _p(dgamma), _p(dbeta), M, Cc, dt_code(z))
+            _p(beta), _p(red), dz.data_ptr() + dz_off * dz.element_size(), _p(dgamma), _p(dbeta), M, Cc,
+            Cc if lddz is None else lddz, dt_code(z))
 
 
 def copy_rows(src, lds, dst, ldd, B, Ho, Wo, shr, Cc, dst_off=0):
@@ -540,6 +542,76 @@ def gather_sum_rows(d, ldd, dsrc, lds, B, Hs, Ws, shr, Cc, accumulate=False, d_o
 
 def detect_unpermute(dpred, dz, ldz, B, HW, na, no):
     _launch("sodt_detect_unpermute", _p(dpred), _p(dz), ldz, B, HW, na, no, dt_code(dz))
+
+
+def detect_splits(M: int, fwd: bool = False) -> int:
+    """M-slices of sodt_detect_fwd / _bwd, at least 16 stages of 32 rows per slice: one workgroup per CU for the backward (its
+    registers allow no second one), two for the forward (60 KiB of LDS each at K = 128: twice the rows in flight per CU)."""
+    return max(1, min(M // 512, 512 if fwd else 256))
+
+
+def detect_fused_ok(K: int, na: int, no: int, dtype: torch.dtype) -> bool:
+    """the shapes sodt_detect_fwd / sodt_detect_bwd take (csrc/detect.hip); alignment is checked by the entry itself"""
+    return dtype == torch.bfloat16 and K % 32 == 0 and 32 <= K <= 256 and 1 <= na * no <= 48
+
+
+def _detect_args(X, W, B, HW, na, no, K, splits, fwd=False):
+    g = L.DetectArgs()
+    g.X, g.ldx = X.data_ptr(), X.shape[-1]
+    g.W, g.ldw = W.data_ptr(), W.stride(0)
+    g.B, g.HW, g.na, g.no, g.K = B, HW, na, no, K
+    g.splits = detect_splits(B * HW, fwd) if splits is None else splits
+    return g
+
+
+def _detect_call(name, g) -> bool:
+    fn = getattr(_lib, name)
+    args = (C.byref(g), L.BF16)
+    rc = fn(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc == L.EINVAL:              # refused before any launch
+        return False
+    if rc != 0:
+        raise RuntimeError(f"{name} failed with status {rc}")
+    if _active_recorder is not None:
+        _active_recorder.append((fn, args, name, _tag))
+    return True
+
+
+def detect_fwd(X: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], pred: torch.Tensor, B: int, HW: int, na: int, no: int,
+               K: int, splits: Optional[int] = None) -> bool:
+    """pred (B, na, HW, no) f32 = Detect's 1x1 convolution of X [B*HW][K] with W [>= na*no][K] (+ bias), in one pass (csrc/detect.hip).
+    Returns False, with nothing launched, written or recorded, where sodt_detect_fwd does not take the call (SODT_EINVAL): the
+    caller then runs gemm_nt(..., detect=...)."""
+    if X.dtype != torch.bfloat16 or W.dtype != torch.bfloat16 or pred.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        return False
+    g = _detect_args(X, W, B, HW, na, no, K, splits, fwd=True)
+    g.bias, g.pred = _p(bias), pred.data_ptr()
+    return _detect_call("sodt_detect_fwd", g)
+
+
+def detect_bwd(dpred: torch.Tensor, X: torch.Tensor, W: torch.Tensor, dX: Optional[torch.Tensor], dW: Optional[torch.Tensor],
+               dbias: Optional[torch.Tensor], B: int, HW: int, na: int, no: int, K: int, *, lddw: Optional[int] = None,
+               splits: Optional[int] = None) -> bool:
+    """Detect's backward from ONE read of dpred (B, na, HW, no) f32: dX [B*HW][K] bf16 = dZ @ W, dW [na*no][K] f32 += dZ^T @ X,
+    dbias += column sums of dZ, with dZ = bf16(dpred).  dX None: no input gradient; dW None: no weight / bias gradient.  The
+    slices' partials go through the weight-gradient scratch (set_tn_scratch).  Returns False, with nothing launched or written,
+    where sodt_detect_bwd refuses (SODT_EINVAL): the caller then runs detect_unpermute + gemm_tn + gemm_nt."""
+    ts = [X, W] + ([dX] if dX is not None else [])
+    if any(t.dtype != torch.bfloat16 for t in ts) or dpred.dtype != torch.float32 or any(t is not None and t.dtype != torch.float32 for t in (dW, dbias)):
+        return False
+    g = _detect_args(X, W, B, HW, na, no, K, splits)
+    g.pred = dpred.data_ptr()
+    if dX is not None:
+        g.dX, g.lddx = dX.data_ptr(), dX.shape[-1]
+    else:
+        g.flags |= L.DETECT_NO_DX
+    if dW is not None:
+        g.dW, g.lddw, g.dbias = dW.data_ptr(), (K if lddw is None else lddw), _p(dbias)
+        if _tn_scratch is not None and _tn_scratch.device == X.device:
+            g.partial, g.partial_floats = _tn_scratch.data_ptr(), _tn_scratch.numel()
+    else:
+        g.flags |= L.DETECT_NO_WGRAD
+    return _detect_call("sodt_detect_bwd", g)
 
 
 def detect_decode(raw, anchor_grid, z, B, na, ny, nx, no, stride):

@@ -56,6 +56,15 @@ def cost(name, args):
         npass = 4 if g.flags & 8 else 3
         return (f"M={g.M} N={g.N} K={g.K} dX+dW{' dgelu' if g.flags & 8 else ''}",
                 g.M * npass * g.N * ES + (2.0 * g.splits + 2) * g.N * g.K * 4 + g.N * g.K * ES, 4.0 * g.M * g.N * g.K)
+    if name in ("sodt_detect_fwd", "sodt_detect_bwd"):
+        g = unwrap(args[0])
+        M, N = g.B * g.HW, g.na * g.no
+        if name == "sodt_detect_fwd":     # X in once, pred (f32, its own layout) out once, the weight
+            return (f"M={M} N={N} K={g.K} Detect fwd", M * (g.K * ES + N * 4) + N * g.K * ES, 2.0 * M * N * g.K)
+        # dpred (f32) and X in once; dX out unless SODT_DETECT_NO_DX; one [48][K] partial per slice written and read unless ..._NO_WGRAD
+        dx, wg = 0 if g.flags & 2 else 1, 0 if g.flags & 1 else 1
+        return (f"M={M} N={N} K={g.K} Detect bwd{'' if dx else ' no dX'}{'' if wg else ' no dW'}",
+                M * (N * 4 + (1 + dx) * g.K * ES) + wg * 2.0 * g.splits * 48 * g.K * 4, 2.0 * (dx + wg) * M * N * g.K)
     if name == "sodt_wmsa_block_fwd":
         B, H, W, C = (val(args[i]) for i in (10, 11, 12, 13))
         T = B * H * W
