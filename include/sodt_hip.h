@@ -365,6 +365,17 @@ int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const 
                       const float* gamma, const float* beta, const void* dout,
                       float* dw, float* db, float* dgamma, float* dbeta, int B, int S, int ca_ws,
                       float* ws, long ws_bytes, int dtype, sodt_stream_t st);
+/* The same on an H x W image: rgb (B,3,H,W), token grid th x tw = H/4 x W/4, output row (b * th + y) * tw + x.  H % 4 or W % 4
+ * non-zero is refused (SODT_EINVAL, nothing launched): the patches are 4 x 4 and are read as 16-byte rows.  The square entries
+ * above are the H == W == S call of these. */
+int sodt_frontend_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                         const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
+                         int dtype, sodt_stream_t st);
+long sodt_frontend_bwd_hw_workspace_bytes(int B, int H, int W);
+int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                         const float* gamma, const float* beta, const void* dout,
+                         float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
+                         float* ws, long ws_bytes, int dtype, sodt_stream_t st);
 
 /* General cross-channel attention (window ca_ws in 1..8, optional cyclic shift; backbone_vit.py:469-561, :589-616) as
  * separate stages: e = 4x Conv2d(1->48,k4,s4) embeddings, f32 [B*t*t][192] (caller's workspace); then per pair
@@ -378,6 +389,16 @@ int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta
                            int shift, int dtype, sodt_stream_t st);
 int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
                            float* dbeta, int B, int S, int ws, int shift, int dtype, sodt_stream_t st);
+/* The same on an H x W image (th x tw tokens): the roll and the 0 / -100 mask run per axis on the th x tw grid; refused unless
+ * H % 4 == W % 4 == 0 and both th and tw are multiples of ws. */
+int sodt_patch_embed4_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                             float* e, int B, int H, int W, sodt_stream_t st);
+int sodt_patch_embed4_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
+                             int B, int H, int W, sodt_stream_t st);
+int sodt_cross_attn_ln_fwd_hw(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W, int ws,
+                              int shift, int dtype, sodt_stream_t st);
+int sodt_cross_attn_ln_bwd_hw(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
+                              float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st);
 
 /* BatchNorm2d (eps 1e-3, momentum 0.03) + SiLU of the head's Conv (common.py:38-50,
  * torch_utils.py:150-152), token-major.  stats f64 [SODT_STATS_REPL][2][C] from SODT_EPI_STATS.

@@ -153,6 +153,12 @@ SIGNATURES = {
     "sodt_patch_embed4_bwd": [_P, _P, _L, _P, _P, _P, _I, _I, _P],
     "sodt_cross_attn_ln_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_cross_attn_ln_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sodt_frontend_fwd_hw": [_P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sodt_frontend_bwd_hw": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _I, _P],
+    "sodt_patch_embed4_fwd_hw": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
+    "sodt_patch_embed4_bwd_hw": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
+    "sodt_cross_attn_ln_fwd_hw": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_cross_attn_ln_bwd_hw": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bn_finalize": [_P, _P, _P, _P, _L, _I, _F, _F, _P],
     "sodt_bn_affine": [_P, _P, _P, _P, _P, _I, _P],
     "sodt_bn_silu_fwd": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
@@ -239,6 +245,8 @@ def load():
     lib.sodt_wmsa_pack_bytes.restype = C.c_long
     lib.sodt_frontend_bwd_workspace_bytes.argtypes = [_I, _I]
     lib.sodt_frontend_bwd_workspace_bytes.restype = C.c_long
+    lib.sodt_frontend_bwd_hw_workspace_bytes.argtypes = [_I, _I, _I]
+    lib.sodt_frontend_bwd_hw_workspace_bytes.restype = C.c_long
     lib.sodt_conv3x3_c64n8_wgrad_scratch_bytes.argtypes = []
     lib.sodt_conv3x3_c64n8_wgrad_scratch_bytes.restype = C.c_long
     lib.sodt_conv3x3_c64_wgrad_scratch_bytes.argtypes = []
@@ -251,4 +259,5 @@ def load():
 
 def exported_symbols():
     return list(SIGNATURES.keys()) + ["sodt_version", "sodt_wmsa_pack_bytes", "sodt_frontend_bwd_workspace_bytes",
+                                           "sodt_frontend_bwd_hw_workspace_bytes",
                                            "sodt_conv3x3_c64n8_wgrad_scratch_bytes", "sodt_conv3x3_c64_wgrad_scratch_bytes"]

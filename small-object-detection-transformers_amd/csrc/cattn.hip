@@ -18,19 +18,19 @@ namespace {
 
 constexpr int CE = 48, NH = 12, HD4 = 4;
 
-struct CaGeo { int B, S, t, ws, shift; long ir_bstride; };
+struct CaGeo { int B, H, W, th, tw, ws, shift; long ir_bstride; };   // image H x W, token grid th x tw = H/4 x W/4
 
 __device__ __forceinline__ void patch16(const float* __restrict__ rgb, const float* __restrict__ ir, const CaGeo& g, int p,
                                         int b, int y, int x, float* pt) {
-  const int S = g.S;
-  const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * S * S);
+  const int H = g.H, W = g.W;
+  const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * H * W);
   const int o = (p == 0) ? -1 : 0;      // channel_embed_r has padding (1,1): backbone_vit.py:69-74,:751
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int yy = 4 * y + o + i, xx = 4 * x + o + j;
-      pt[i * 4 + j] = (yy >= 0 && xx >= 0 && yy < S && xx < S) ? base[(long)yy * S + xx] : 0.f;
+      pt[i * 4 + j] = (yy >= 0 && xx >= 0 && yy < H && xx < W) ? base[(long)yy * W + xx] : 0.f;
     }
 }
 
@@ -40,9 +40,9 @@ __global__ __launch_bounds__(256) void patch_embed4_fwd_kernel(const float* __re
   const long i = (long)blockIdx.x * 256 + threadIdx.x;    // one thread per (token, plane)
   if (i >= ntok * 4) return;
   const long tok = i >> 2; const int p = (int)(i & 3);
-  const int tt = g.t * g.t;
+  const int tt = g.th * g.tw;
   const int b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt);
-  const int y = rem / g.t, x = rem - y * g.t;
+  const int y = rem / g.tw, x = rem - y * g.tw;
   float pt[16];
   patch16(rgb, ir, g, p, b, y, x, pt);
   const float* wp = w + p * CE * 16;
@@ -61,17 +61,17 @@ __global__ __launch_bounds__(256) void patch_embed4_bwd_kernel(const float* __re
   const int oid = blockIdx.x * 256 + threadIdx.x;       // 0 .. 4*48*17-1  (tap 16 = bias)
   if (oid >= 4 * CE * 17) return;
   const int p = oid / (CE * 17), r = oid - p * CE * 17, j = r / 17, k = r - j * 17;
-  const int tt = g.t * g.t;
+  const int tt = g.th * g.tw;
   float acc = 0.f;
   for (long tok = blockIdx.y; tok < ntok; tok += gridDim.y) {
     const float d = de[tok * 192 + p * CE + j];
     if (k == 16) { acc += d; continue; }
     const int b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt);
-    const int y = rem / g.t, x = rem - y * g.t;
+    const int y = rem / g.tw, x = rem - y * g.tw;
     const int o = (p == 0) ? -1 : 0;
     const int yy = 4 * y + o + (k >> 2), xx = 4 * x + o + (k & 3);
-    const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * g.S * g.S);
-    const float v = (yy >= 0 && xx >= 0 && yy < g.S && xx < g.S) ? base[(long)yy * g.S + xx] : 0.f;
+    const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * g.H * g.W);
+    const float v = (yy >= 0 && xx >= 0 && yy < g.H && xx < g.W) ? base[(long)yy * g.W + xx] : 0.f;
     acc = fmaf(d, v, acc);
   }
   if (k == 16) atomicAdd(db + p * CE + j, acc);
@@ -83,25 +83,25 @@ __device__ __forceinline__ int pair_kv(int q) { return q == 0 ? 1 : (q == 1 ? 2 
 // window geometry of token (b, y, x) under roll(-shift): window origin in shifted coordinates + mask region id
 __device__ __forceinline__ void ca_window(const CaGeo& g, int y, int x, int& ys0, int& xs0, int& rid) {
   int ys = y - g.shift, xs = x - g.shift;               // shifted[ys] = x[(ys + shift) % H]
-  if (ys < 0) ys += g.t;
-  if (xs < 0) xs += g.t;
+  if (ys < 0) ys += g.th;
+  if (xs < 0) xs += g.tw;
   ys0 = ys / g.ws * g.ws; xs0 = xs / g.ws * g.ws;
   rid = 0;
   if (g.shift > 0) {
-    const int ry = ys < g.t - g.ws ? 0 : (ys < g.t - g.shift ? 1 : 2);
-    const int rx = xs < g.t - g.ws ? 0 : (xs < g.t - g.shift ? 1 : 2);
+    const int ry = ys < g.th - g.ws ? 0 : (ys < g.th - g.shift ? 1 : 2);
+    const int rx = xs < g.tw - g.ws ? 0 : (xs < g.tw - g.shift ? 1 : 2);
     rid = ry * 3 + rx;
   }
 }
 __device__ __forceinline__ void ca_key(const CaGeo& g, int ys0, int xs0, int n, int& ky, int& kx, int& krid) {
   const int iy = n / g.ws, ix = n - iy * g.ws;
   const int ys = ys0 + iy, xs = xs0 + ix;
-  ky = ys + g.shift; if (ky >= g.t) ky -= g.t;
-  kx = xs + g.shift; if (kx >= g.t) kx -= g.t;
+  ky = ys + g.shift; if (ky >= g.th) ky -= g.th;
+  kx = xs + g.shift; if (kx >= g.tw) kx -= g.tw;
   krid = 0;
   if (g.shift > 0) {
-    const int ry = ys < g.t - g.ws ? 0 : (ys < g.t - g.shift ? 1 : 2);
-    const int rx = xs < g.t - g.ws ? 0 : (xs < g.t - g.shift ? 1 : 2);
+    const int ry = ys < g.th - g.ws ? 0 : (ys < g.th - g.shift ? 1 : 2);
+    const int rx = xs < g.tw - g.ws ? 0 : (xs < g.tw - g.shift ? 1 : 2);
     krid = ry * 3 + rx;
   }
 }
@@ -113,9 +113,9 @@ __global__ __launch_bounds__(128) void cross_attn_ln_fwd_kernel(const float* __r
   const long i = (long)blockIdx.x * 128 + threadIdx.x;
   if (i >= ntok * 4) return;
   const long tok = i >> 2; const int p = (int)(i & 3), kvp = pair_kv(p);
-  const int tt = g.t * g.t, N = g.ws * g.ws;
+  const int tt = g.th * g.tw, N = g.ws * g.ws;
   const int b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt);
-  const int y = rem / g.t, x = rem - y * g.t;
+  const int y = rem / g.tw, x = rem - y * g.tw;
   int ys0, xs0, qrid;
   ca_window(g, y, x, ys0, xs0, qrid);
   const float* qrow = e + tok * 192 + p * CE;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(128) void cross_attn_ln_fwd_kernel(const float* __r
     for (int n = 0; n < N; ++n) {       // online softmax over the window's keys
       int ky, kx, krid;
       ca_key(g, ys0, xs0, n, ky, kx, krid);
-      const float4 k = *(const float4*)(e + ((long)(b * g.t + ky) * g.t + kx) * 192 + kvp * CE + h * HD4);
+      const float4 k = *(const float4*)(e + ((long)(b * g.th + ky) * g.tw + kx) * 192 + kvp * CE + h * HD4);
       float sc = q.x * k.x + q.y * k.y + q.z * k.z + q.w * k.w;
       if (qrid != krid) sc += -100.0f;
       sc *= 0.5f;                        // / sqrt(4), after the mask
@@ -161,9 +161,9 @@ __global__ __launch_bounds__(128) void cross_attn_ln_bwd_kernel(const float* __r
   const long i = (long)blockIdx.x * 128 + threadIdx.x;
   const bool live = i < ntok * 4;
   const long tok = live ? (i >> 2) : 0; const int p = (int)(i & 3), kvp = pair_kv(p);
-  const int tt = g.t * g.t, N = g.ws * g.ws;
+  const int tt = g.th * g.tw, N = g.ws * g.ws;
   const int b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt);
-  const int y = rem / g.t, x = rem - y * g.t;
+  const int y = rem / g.tw, x = rem - y * g.tw;
   int ys0, xs0, qrid;
   ca_window(g, y, x, ys0, xs0, qrid);
   const float* qrow = e + tok * 192 + p * CE;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(128) void cross_attn_ln_bwd_kernel(const float* __r
     for (int n = 0; n < N; ++n) {
       int ky, kx, krid;
       ca_key(g, ys0, xs0, n, ky, kx, krid);
-      const float4 k = *(const float4*)(e + ((long)(b * g.t + ky) * g.t + kx) * 192 + kvp * CE + h * HD4);
+      const float4 k = *(const float4*)(e + ((long)(b * g.th + ky) * g.tw + kx) * 192 + kvp * CE + h * HD4);
       float sc = q.x * k.x + q.y * k.y + q.z * k.z + q.w * k.w;
       if (qrid != krid) sc += -100.0f;
       sc *= 0.5f;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(128) void cross_attn_ln_bwd_kernel(const float* __r
     for (int n = 0; n < N; ++n) {
       int ky, kx, krid;
       ca_key(g, ys0, xs0, n, ky, kx, krid);
-      const float4 k = *(const float4*)(e + ((long)(b * g.t + ky) * g.t + kx) * 192 + kvp * CE + h * HD4);
+      const float4 k = *(const float4*)(e + ((long)(b * g.th + ky) * g.tw + kx) * 192 + kvp * CE + h * HD4);
       float sc = q.x * k.x + q.y * k.y + q.z * k.z + q.w * k.w;
       if (qrid != krid) sc += -100.0f;
       sc *= 0.5f;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(128) void cross_attn_ln_bwd_kernel(const float* __r
     for (int n = 0; n < N; ++n) {
       int ky, kx, krid;
       ca_key(g, ys0, xs0, n, ky, kx, krid);
-      const long krow = ((long)(b * g.t + ky) * g.t + kx) * 192 + kvp * CE + h * HD4;
+      const long krow = ((long)(b * g.th + ky) * g.tw + kx) * 192 + kvp * CE + h * HD4;
       const float4 k = *(const float4*)(e + krow);
       float sc = q.x * k.x + q.y * k.y + q.z * k.z + q.w * k.w;
       if (qrid != krid) sc += -100.0f;
@@ -261,49 +261,69 @@ __global__ __launch_bounds__(128) void cross_attn_ln_bwd_kernel(const float* __r
   }
 }
 
-bool ca_geo(CaGeo& g, int B, int S, int ws, int shift, long ir_bstride) {
-  if (B <= 0 || S <= 0 || (S % 4) || ws < 1 || ws > 8 || shift < 0 || shift >= (ws > 1 ? ws : 1)) return false;
-  g.B = B; g.S = S; g.t = S / 4; g.ws = ws; g.shift = shift; g.ir_bstride = ir_bstride;
-  return (g.t % ws) == 0;
+bool ca_geo(CaGeo& g, int B, int H, int W, int ws, int shift, long ir_bstride) {
+  if (B <= 0 || H <= 0 || W <= 0 || (H % 4) || (W % 4) || ws < 1 || ws > 8 || shift < 0 || shift >= (ws > 1 ? ws : 1)) return false;
+  g.B = B; g.H = H; g.W = W; g.th = H / 4; g.tw = W / 4; g.ws = ws; g.shift = shift; g.ir_bstride = ir_bstride;
+  return (g.th % ws) == 0 && (g.tw % ws) == 0;
 }
 
 }  // namespace
 
-extern "C" int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                     float* e, int B, int S, sodt_stream_t st) {
+extern "C" int sodt_patch_embed4_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                        float* e, int B, int H, int W, sodt_stream_t st) {
   CaGeo g;
-  if (!rgb || !ir || !w || !b || !e || !ca_geo(g, B, S, 1, 0, ir_bstride)) return SODT_EINVAL;
-  const long ntok = (long)B * g.t * g.t;
+  if (!rgb || !ir || !w || !b || !e || !ca_geo(g, B, H, W, 1, 0, ir_bstride)) return SODT_EINVAL;
+  const long ntok = (long)B * g.th * g.tw;
   return sodt_launch<patch_embed4_fwd_kernel>(dim3((unsigned)((ntok * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, e, g, ntok);
 }
 
-extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
-                                     int B, int S, sodt_stream_t st) {
+extern "C" int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                     float* e, int B, int S, sodt_stream_t st) {
+  return sodt_patch_embed4_fwd_hw(rgb, ir, ir_bstride, w, b, e, B, S, S, st);
+}
+
+extern "C" int sodt_patch_embed4_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
+                                        int B, int H, int W, sodt_stream_t st) {
   CaGeo g;
-  if (!rgb || !ir || !de || !dw || !db || !ca_geo(g, B, S, 1, 0, ir_bstride)) return SODT_EINVAL;
-  const long ntok = (long)B * g.t * g.t;
+  if (!rgb || !ir || !de || !dw || !db || !ca_geo(g, B, H, W, 1, 0, ir_bstride)) return SODT_EINVAL;
+  const long ntok = (long)B * g.th * g.tw;
   const unsigned gy = (unsigned)(ntok < 512 ? ntok : 512);
   return sodt_launch<patch_embed4_bwd_kernel>(dim3((4 * CE * 17 + 255) / 256, gy), dim3(256), 0, (hipStream_t)st, rgb, ir, de, dw, db, g, ntok);
 }
 
-extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int S, int ws,
-                                      int shift, int dtype, sodt_stream_t st) {
+extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
+                                     int B, int S, sodt_stream_t st) {
+  return sodt_patch_embed4_bwd_hw(rgb, ir, ir_bstride, de, dw, db, B, S, S, st);
+}
+
+extern "C" int sodt_cross_attn_ln_fwd_hw(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W,
+                                         int ws, int shift, int dtype, sodt_stream_t st) {
   CaGeo g;
-  if (!e || !gamma || !beta || !out || !ca_geo(g, B, S, ws, shift, 0)) return SODT_EINVAL;
-  const long ntok = (long)B * g.t * g.t;
+  if (!e || !gamma || !beta || !out || !ca_geo(g, B, H, W, ws, shift, 0)) return SODT_EINVAL;
+  const long ntok = (long)B * g.th * g.tw;
   const unsigned gr = (unsigned)((ntok * 4 + 127) / 128);
   if (dtype == SODT_BF16) return sodt_launch<cross_attn_ln_fwd_kernel<bf16>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (bf16*)out, g, ntok);
   if (dtype == SODT_F32) return sodt_launch<cross_attn_ln_fwd_kernel<float>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, beta, (float*)out, g, ntok);
   return SODT_EINVAL;
 }
 
-extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
-                                      float* dbeta, int B, int S, int ws, int shift, int dtype, sodt_stream_t st) {
+extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int S, int ws,
+                                      int shift, int dtype, sodt_stream_t st) {
+  return sodt_cross_attn_ln_fwd_hw(e, gamma, beta, out, B, S, S, ws, shift, dtype, st);
+}
+
+extern "C" int sodt_cross_attn_ln_bwd_hw(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
+                                         float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st) {
   CaGeo g;
-  if (!e || !gamma || !dout || !de || !dgamma || !dbeta || !ca_geo(g, B, S, ws, shift, 0)) return SODT_EINVAL;
-  const long ntok = (long)B * g.t * g.t;
+  if (!e || !gamma || !dout || !de || !dgamma || !dbeta || !ca_geo(g, B, H, W, ws, shift, 0)) return SODT_EINVAL;
+  const long ntok = (long)B * g.th * g.tw;
   const unsigned gr = (unsigned)((ntok * 4 + 127) / 128);
   if (dtype == SODT_BF16) return sodt_launch<cross_attn_ln_bwd_kernel<bf16>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const bf16*)dout, de, dgamma, dbeta, g, ntok);
   if (dtype == SODT_F32) return sodt_launch<cross_attn_ln_bwd_kernel<float>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const float*)dout, de, dgamma, dbeta, g, ntok);
   return SODT_EINVAL;
+}
+
+extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
+                                      float* dbeta, int B, int S, int ws, int shift, int dtype, sodt_stream_t st) {
+  return sodt_cross_attn_ln_bwd_hw(e, gamma, dout, de, dgamma, dbeta, B, S, S, ws, shift, dtype, st);
 }

@@ -4,12 +4,12 @@
 //   CAttentionBlock                   (:469-561)   pairs (R<-G),(G<-B),(B<-IR),(IR<-G),
 //                                                  12 heads x 4, softmax(q k^T / 2) v,
 //                                                  residual, LayerNorm(48)
-//   torch.cat(dim=-1)                 (:210)       -> [B*t*t][192] token-major
+//   torch.cat(dim=-1)                 (:210)       -> [B*th*tw][192] token-major (th x tw = H/4 x W/4 tokens of an H x W image)
 // With the shipped window_size = 1 (:438) every window holds one token, softmax over
 // one key is exactly 1, and the block reduces to x_q = LN_q(e_q + e_kv): that is the
-// ca_ws == 1 path below.  HBM-bound: reads 4*S*S f32, writes t*t*192 activations.
+// ca_ws == 1 path below.  HBM-bound: reads 4*H*W f32, writes th*tw*192 activations.
 //
-// One workgroup = 64 consecutive tokens; wave p computes plane p's 48-channel embedding
+// One workgroup = 64 consecutive tokens (rows of the output: it may straddle token rows and images); wave p computes plane p's 48-channel embedding
 // for its token (weights are wave-uniform -> scalar loads), the four embeddings meet in
 // LDS, wave q then forms pair q's sum + LayerNorm, and the 64x192 output block (contiguous
 // in memory) is written with 16-byte stores.  Backward recomputes the embeddings from
@@ -26,28 +26,29 @@ constexpr int EP = CE + 1;  // padded LDS row (floats)
 constexpr int FE_PART = 4 * CE * 19;   // partial sums of one backward workgroup: per plane/pair dW[48][16] | dgamma | dbeta | sum d(pair sum)
 constexpr int FE_BWD_GRID = 512;       // two resident workgroups per CU (66 KB of LDS each)
 
-struct FeGeo { int B, S, t; long ir_bstride; };
+struct FeGeo { int B, H, W, th, tw; long ir_bstride; };   // image H x W, token grid th x tw = H/4 x W/4
 
 // 4x4 patch of plane p for token (b, y, x): R (p == 0) is shifted by -1 with zero padding
 __device__ __forceinline__ void load_patch(const float* __restrict__ rgb, const float* __restrict__ ir, const FeGeo& g,
                                            int p, int b, int y, int x, float* pt) {
-  const int S = g.S;
+  const int H = g.H, W = g.W;
+  const long plane = (long)H * W;
   if (p == 0) {
-    const float* base = rgb + (long)b * 3 * S * S;
+    const float* base = rgb + (long)b * 3 * plane;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int yy = 4 * y - 1 + i;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int xx = 4 * x - 1 + j;
-        pt[i * 4 + j] = (yy >= 0 && xx >= 0 && yy < S && xx < S) ? base[(long)yy * S + xx] : 0.f;
+        pt[i * 4 + j] = (yy >= 0 && xx >= 0 && yy < H && xx < W) ? base[(long)yy * W + xx] : 0.f;
       }
     }
   } else {
-    const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * S * S);
+    const float* base = (p == 3) ? (ir + (long)b * g.ir_bstride) : (rgb + ((long)b * 3 + p) * plane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float4 v = *(const float4*)(base + (long)(4 * y + i) * S + 4 * x);
+      const float4 v = *(const float4*)(base + (long)(4 * y + i) * W + 4 * x);   // 16-byte aligned: W % 4 == 0
       pt[i * 4] = v.x; pt[i * 4 + 1] = v.y; pt[i * 4 + 2] = v.z; pt[i * 4 + 3] = v.w;
     }
   }
@@ -72,9 +73,9 @@ __global__ __launch_bounds__(256) void frontend_fwd_kernel(const float* __restri
   const long tok0 = (long)blockIdx.x * 64;
   const long tok = tok0 + lane;
   const bool live = tok < ntok;
-  const int tt = g.t * g.t;
+  const int tt = g.th * g.tw;
   int b = 0, y = 0, x = 0;
-  if (live) { b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt); y = rem / g.t; x = rem - y * g.t; }
+  if (live) { b = (int)(tok / tt); const int rem = (int)(tok - (long)b * tt); y = rem / g.tw; x = rem - y * g.tw; }
   float pt[16];
   if (live) load_patch(rgb, ir, g, p, b, y, x, pt);
   else {
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void frontend_bwd_kernel(const float* __res
   __shared__ float sP[4][64][17];    // patches
   const int tid = threadIdx.x, lane = tid & 63;
   const int p = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tt = g.t * g.t;
+  const int tt = g.th * g.tw;
   const float* wp = w + p * CE * 16;
   const float* bp = bias + p * CE;
   const float* gp = gamma + p * CE;
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void frontend_bwd_kernel(const float* __res
     if (blk < nblk && tok < ntok) {
       const int b = (int)(tok / tt);
       const int rem = (int)(tok - (long)b * tt);
-      const int y = rem / g.t, x = rem - y * g.t;
+      const int y = rem / g.tw, x = rem - y * g.tw;
       load_patch(rgb, ir, g, p, b, y, x, pt);
     } else {
 #pragma unroll
@@ -364,15 +365,22 @@ __global__ __launch_bounds__(64) void frontend_bwd_reduce_kernel(const float* __
   }
 }
 
+// H x W image -> th x tw tokens; false = refused (the 16-byte patch loads need W % 4 == 0, the 4 x 4 patches H % 4 == 0)
+bool fe_geo(FeGeo& g, int B, int H, int W, long ir_bstride) {
+  if (B <= 0 || H <= 0 || W <= 0 || (H % 4) || (W % 4)) return false;
+  g.B = B; g.H = H; g.W = W; g.th = H / 4; g.tw = W / 4; g.ir_bstride = ir_bstride;
+  return true;
+}
+
 }  // namespace
 
-extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                 const float* gamma, const float* beta, void* out, int B, int S, int ca_ws,
-                                 int dtype, sodt_stream_t st) {
-  if (!rgb || !ir || !w || !b || !gamma || !beta || !out || B <= 0 || S <= 0 || (S % 4)) return SODT_EINVAL;
+extern "C" int sodt_frontend_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                    const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
+                                    int dtype, sodt_stream_t st) {
+  FeGeo g;
+  if (!rgb || !ir || !w || !b || !gamma || !beta || !out || !fe_geo(g, B, H, W, ir_bstride)) return SODT_EINVAL;
   if (ca_ws != 1) return SODT_EINVAL;   // general window path: sodt_cross_channel_attn_* (cattn.hip)
-  FeGeo g{B, S, S / 4, ir_bstride};
-  const long ntok = (long)B * g.t * g.t;
+  const long ntok = (long)B * g.th * g.tw;
   const unsigned blocks = (unsigned)((ntok + 63) / 64);
   if (dtype == SODT_BF16)
     return sodt_launch<frontend_fwd_kernel<bf16>>(dim3(blocks), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, gamma, beta, (bf16*)out, g, ntok);
@@ -381,25 +389,33 @@ extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstr
   return SODT_EINVAL;
 }
 
-extern "C" long sodt_frontend_bwd_workspace_bytes(int B, int S) {
-  (void)B; (void)S;
+extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                 const float* gamma, const float* beta, void* out, int B, int S, int ca_ws,
+                                 int dtype, sodt_stream_t st) {
+  return sodt_frontend_fwd_hw(rgb, ir, ir_bstride, w, b, gamma, beta, out, B, S, S, ca_ws, dtype, st);
+}
+
+extern "C" long sodt_frontend_bwd_hw_workspace_bytes(int B, int H, int W) {
+  (void)B; (void)H; (void)W;
   return (long)FE_BWD_GRID * FE_PART * (long)sizeof(float);
 }
 
-extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                 const float* gamma, const float* beta, const void* dout,
-                                 float* dw, float* db, float* dgamma, float* dbeta, int B, int S, int ca_ws,
-                                 float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
+extern "C" long sodt_frontend_bwd_workspace_bytes(int B, int S) { return sodt_frontend_bwd_hw_workspace_bytes(B, S, S); }
+
+extern "C" int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                    const float* gamma, const float* beta, const void* dout,
+                                    float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
+                                    float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
   (void)beta;
-  if (!rgb || !ir || !w || !b || !gamma || !dout || !dw || !db || !dgamma || !dbeta || B <= 0 || S <= 0 || (S % 4)) return SODT_EINVAL;
+  FeGeo g;
+  if (!rgb || !ir || !w || !b || !gamma || !dout || !dw || !db || !dgamma || !dbeta || !fe_geo(g, B, H, W, ir_bstride)) return SODT_EINVAL;
   if (ca_ws != 1) return SODT_EINVAL;
   if (dtype != SODT_BF16 && dtype != SODT_F32) return SODT_EINVAL;
-  FeGeo g{B, S, S / 4, ir_bstride};
-  const long ntok = (long)B * g.t * g.t;
+  const long ntok = (long)B * g.th * g.tw;
   const int nblk = (int)((ntok + 63) / 64);
   // the two-stage reduction pays once there are enough workgroups for the direct atomics to queue up; without a
   // workspace fewer, longer-lived workgroups keep the final burst of atomics short
-  const bool two_stage = ws && ws_bytes >= sodt_frontend_bwd_workspace_bytes(B, S) && nblk > 64;
+  const bool two_stage = ws && ws_bytes >= sodt_frontend_bwd_hw_workspace_bytes(B, H, W) && nblk > 64;
   const int cap = two_stage ? FE_BWD_GRID : FE_BWD_GRID / 2;
   const unsigned blocks = (unsigned)(nblk < cap ? nblk : cap);
   hipStream_t s = (hipStream_t)st;
@@ -411,4 +427,11 @@ extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstr
   if (rc || !two_stage) return rc;
   return sodt_launch<frontend_bwd_reduce_kernel>(dim3(FE_PART / 64, (blocks + FE_RG - 1) / FE_RG), dim3(64), 0, s, ws, (int)blocks,
                                                  dw, db, dgamma, dbeta);
+}
+
+extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                 const float* gamma, const float* beta, const void* dout,
+                                 float* dw, float* db, float* dgamma, float* dbeta, int B, int S, int ca_ws,
+                                 float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
+  return sodt_frontend_bwd_hw(rgb, ir, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, S, S, ca_ws, ws, ws_bytes, dtype, st);
 }

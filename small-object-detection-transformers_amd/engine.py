@@ -47,7 +47,10 @@ class _EveryUnit:
 
 class Plan:
     def __init__(self, B, S, dt, training, dev, fz=None):
-        self.B, self.S, self.dt, self.training, self.dev = B, S, dt, training, dev
+        # S: the side of a square input, or (H, W).  plan.S stays the int for a square plan and is the tuple for H != W
+        H, W = (S, S) if isinstance(S, int) else (int(S[0]), int(S[1]))
+        S = H if H == W else (H, W)
+        self.B, self.S, self.H, self.W, self.dt, self.training, self.dev = B, S, H, W, dt, training, dev
         self.fz: Optional[freeze.FreezeRecord] = fz     # what the requires_grad flags leave of the backward (training plans of Engine.run)
         self.bufs: Dict[str, torch.Tensor] = {}
         self.bwd_marks: List[Tuple[int, int, int]] = []   # (index in bwd_main, first, last+1 element of flat_grad) of the
@@ -131,7 +134,8 @@ class Plan:
 
 class _Plans(dict):
     """Engine.plans: (B, S, dt, False) -> eval plan, (B, S, dt, True, freeze signature) -> training plan.  The four-entry key of a
-    training plan reads the plan with nothing frozen (signature 0), which is what it named before plans knew about freezing."""
+    training plan reads the plan with nothing frozen (signature 0), which is what it named before plans knew about freezing.
+    S is the side of a square input; an H x W input with H != W has (H, W) in that slot."""
 
     def __missing__(self, key):
         if len(key) == 4 and key[3] and key + (0,) in self:
@@ -523,13 +527,20 @@ class Engine:
     MAX_PLANS = 4      # each plan owns a full activation workspace (31 GB at B=8 @1024^2 bf16): least recently used goes
 
     def run(self, x_rgb, x_ir, dt, training):
-        if x_rgb.dim() != 4 or x_rgb.shape[1] != 3 or x_ir.dim() != 4 or x_rgb.shape[-1] != x_rgb.shape[-2]:
-            raise ValueError("expected x_rgb (B,3,S,S) and x_ir (B,>=1,S,S)")
-        B, _, S, _ = x_rgb.shape
-        if S % 32:
-            raise ValueError("S must be a multiple of 32 (4x patch stride, 8x8 windows on t/2 .. even t/4)")
-        if x_ir.shape[0] != B or x_ir.shape[1] < 1 or tuple(x_ir.shape[-2:]) != (S, S):
-            raise ValueError(f"x_ir must be (B={B}, >=1, {S}, {S}) like x_rgb, got {tuple(x_ir.shape)}")
+        if x_rgb.dim() != 4 or x_rgb.shape[1] != 3 or x_ir.dim() != 4:
+            raise ValueError("expected x_rgb (B,3,H,W) and x_ir (B,>=1,H,W)")
+        B, _, H, W = x_rgb.shape
+        if H % 32 or W % 32:
+            raise ValueError(f"H and W must be multiples of 32 (4x patch stride, 8x8 windows on t/2 .. even t/4), got {H} x {W}")
+        if x_ir.shape[0] != B or x_ir.shape[1] < 1 or tuple(x_ir.shape[-2:]) != (H, W):
+            raise ValueError(f"x_ir must be (B={B}, >=1, {H}, {W}) like x_rgb, got {tuple(x_ir.shape)}")
+        if H != W and self.sr:
+            raise NotImplementedError(f"Model(sr=True) runs square inputs only: the super-resolution branch is not built for {H} x {W}")
+        if H // 4 == self.img_t and W // 4 != self.img_t:
+            # backbone_vit.py:215-217 compares the ROWS alone and then fails to broadcast; say so before any launch
+            raise ValueError(f"pos_embed is {self.img_t} x {self.img_t} tokens: a {H} x {W} input has its {H // 4} rows and {W // 4} columns, "
+                             "which the reference adds and cannot broadcast (backbone_vit.py:215-217); use another height")
+        S = H if H == W else (H, W)
         if x_rgb.device != self.dev or x_ir.device != self.dev:
             raise ValueError(f"inputs must be on the model's device {self.dev} (got {x_rgb.device}, {x_ir.device}): "
                              "the kernels take raw device pointers")
@@ -573,14 +584,14 @@ class Engine:
         next forward).  y4, y5, y8, y9 (upsample / concat) are never materialised by the kernels: the list
         builds them with torch on first access (``_LazyFeatures``), so callers that index them get tensors
         as in the reference and nobody else pays for them."""
-        B, t = plan.B, plan.S // 4
+        B, th, tw = plan.B, plan.H // 4, plan.W // 4
         b = plan.bufs
 
-        def nchw(name, h, c):
-            return b[name].view(B, h, h, c).permute(0, 3, 1, 2)
-        items = [nchw("f0", t, 256), nchw("f1", t // 2, 256), nchw("f2", t // 4, 512)] + [None] * self.head.nd
+        def nchw(name, level, c):
+            return b[name].view(B, th >> level, tw >> level, c).permute(0, 3, 1, 2)
+        items = [nchw("f0", 0, 256), nchw("f1", 1, 256), nchw("f2", 2, 512)] + [None] * self.head.nd
         for u in self.head.units:
-            items[3 + u.k] = nchw(u.out_name, t >> u.level, u.c2)
+            items[3 + u.k] = nchw(u.out_name, u.level, u.c2)
         y = _LazyFeatures(items, self.head.rules)
         if self.model.materialize_features:
             for i in sorted(self.head.rules):
@@ -590,8 +601,9 @@ class Engine:
     # ================================================================== forward
     def _forward(self, plan: Plan, x_rgb, x_ir):
         P = self._prep_for(plan.dt)
-        B, S = plan.B, plan.S
-        t = S // 4
+        B, H, W = plan.B, plan.H, plan.W
+        th, tw = H // 4, W // 4
+        T1 = B * th * tw
         plan.gen += 1          # the saved activations of an earlier forward on this plan are gone (see _EngineFn.backward)
         # (0) run-dtype mirror of the masters: written by the fused optimizer step; re-cast here when anything else may have
         #     changed them (live call: the decision is per step)
@@ -609,16 +621,25 @@ class Engine:
         else:
             ops.replay(plan.fwd_pre)
         # (2) front end: live call (input pointers change per step)
-        x0 = plan.buf("x0", (B * t * t, 192))
+        x0 = plan.buf("x0", (T1, 192))
         fe = P["fe"]
         cb = self.model.image_encoder.chan_block
         ca_ws, ca_shift = int(cb.window_size), int(cb.shift_size)
+        irs = x_ir.shape[1] * H * W
+        # a square input keeps the square entry points (and their names in every recorded list); H != W takes the _hw ones
         if ca_ws == 1:      # the shipped configuration (backbone_vit.py:438): fused kernel
-            ops.frontend_fwd(x_rgb, x_ir, x_ir.shape[1] * S * S, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, S, 1)
+            if H == W:
+                ops.frontend_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, H, 1)
+            else:
+                ops.frontend_fwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, H, W, 1)
         else:               # general window / shift form of CAttentionBlock
-            e = plan.buf("fe.e", (B * t * t, 192), torch.float32)
-            ops.patch_embed4_fwd(x_rgb, x_ir, x_ir.shape[1] * S * S, fe["w"], fe["b"], e, B, S)
-            ops.cross_attn_ln_fwd(e, fe["g"], fe["be"], x0, B, S, ca_ws, ca_shift)
+            e = plan.buf("fe.e", (T1, 192), torch.float32)
+            if H == W:
+                ops.patch_embed4_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], e, B, H)
+                ops.cross_attn_ln_fwd(e, fe["g"], fe["be"], x0, B, H, ca_ws, ca_shift)
+            else:
+                ops.patch_embed4_fwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], e, B, H, W)
+                ops.cross_attn_ln_fwd_hw(e, fe["g"], fe["be"], x0, B, H, W, ca_ws, ca_shift)
         # (3) encoder + head (recorded)
         if plan.fwd_main is None:
             with ops.Recorder() as rec:
@@ -627,13 +648,12 @@ class Engine:
         else:
             self._replay(plan, "fwd_main", plan.fwd_main, self.probes_fwd)
         # (4) Detect: live (fresh output tensor every call)
-        T1 = B * t * t
-        pred = torch.empty(B, self.na, t, t, self.no, device=self.dev, dtype=torch.float32)
+        pred = torch.empty(B, self.na, th, tw, self.no, device=self.dev, dtype=torch.float32)
         hrow, hc = self.head.head_out
         hx, wd, bd = self._ref_buf(plan, Ref("unit", hrow)), P["w"][self.det_name + "m.0.weight"], self.params[self.det_name + "m.0.bias"]
         if not (self.use_fused_detect and ops.detect_fused_ok(hc, self.na, self.no, plan.dt)
-                and ops.detect_fwd(hx, wd, bd, pred, B, t * t, self.na, self.no, hc)):
-            ops.gemm_nt([SegSpec(hx)], wd, pred, T1, self.na * self.no, hc, bias=bd, detect=(self.na, self.no, t * t))
+                and ops.detect_fwd(hx, wd, bd, pred, B, th * tw, self.na, self.no, hc)):
+            ops.gemm_nt([SegSpec(hx)], wd, pred, T1, self.na * self.no, hc, bias=bd, detect=(self.na, self.no, th * tw))
         return pred
 
     def _replay(self, plan: Plan, key: str, calls, probes):
@@ -657,63 +677,63 @@ class Engine:
         g.replay()
 
     def _forward_main(self, plan: Plan, P):
-        B, S = plan.B, plan.S
-        t = S // 4
+        B = plan.B
+        H, W = plan.H // 4, plan.W // 4
         p, w = self.params, P["w"]
-        T1 = B * t * t
+        T1 = B * H * W
         x0 = plan.bufs["x0"]
         if plan.training and not self.fused:
             ops.zero_(plan.zpool("f"))               # BatchNorm column-statistics accumulators of every head conv
-        # 1x1 token-mixing conv + bias + pos_embed (only when t matches: backbone_vit.py:215-217)
+        # 1x1 token-mixing conv + bias + pos_embed (only when the rows match: backbone_vit.py:215-217; rows that match with columns
+        # that do not were refused by run())
         x = plan.buf("xe", (T1, 192))
-        use_pos = (t == self.img_t)
+        use_pos = (H == self.img_t and W == self.img_t)
         plan.saved["use_pos"] = use_pos
         ops.gemm_nt([SegSpec(x0)], w[E + "patch_embed.proj.weight"], x, T1, 192, 192, bias=p[E + "patch_embed.proj.bias"],
-                    resid=w[E + "pos_embed"] if use_pos else None, rmod=t * t if use_pos else 0)
+                    resid=w[E + "pos_embed"] if use_pos else None, rmod=H * W if use_pos else 0)
         enc = self.model.image_encoder
         outs = {}
-        H = t
         for i, blk in enumerate(enc.stage1):
-            x = self._block_fwd(plan, P, f"stage1.{i}", blk, x, B, H, H)
+            x = self._block_fwd(plan, P, f"stage1.{i}", blk, x, B, H, W)
             outs[i] = x
         f0 = plan.buf("f0", (T1, 256))
         ops.gemm_nt([SegSpec(outs[4]), SegSpec(outs[5])], w[E + "neck1.weight"], f0, T1, 256, 384)
-        x = self._merge_fwd(plan, P, "pmerging1", x, B, H, H, 192)
-        H //= 2
+        x = self._merge_fwd(plan, P, "pmerging1", x, B, H, W, 192)
+        H, W = H // 2, W // 2
         for i, blk in enumerate(enc.stage2):
-            x = self._block_fwd(plan, P, f"stage2.{i}", blk, x, B, H, H)
-        T2 = B * H * H
+            x = self._block_fwd(plan, P, f"stage2.{i}", blk, x, B, H, W)
+        T2 = B * H * W
         f1 = plan.buf("f1", (T2, 256))
         ops.gemm_nt([SegSpec(x)], w[E + "neck2.weight"], f1, T2, 256, 384)
-        x = self._merge_fwd(plan, P, "pmerging2", x, B, H, H, 384)
-        H //= 2
+        x = self._merge_fwd(plan, P, "pmerging2", x, B, H, W, 384)
+        H, W = H // 2, W // 2
         for i, blk in enumerate(enc.stage3):
-            x = self._block_fwd(plan, P, f"stage3.{i}", blk, x, B, H, H)
-        T3 = B * H * H
+            x = self._block_fwd(plan, P, f"stage3.{i}", blk, x, B, H, W)
+        T3 = B * H * W
         f2 = plan.buf("f2", (T3, 512))
         ops.gemm_nt([SegSpec(x)], w[E + "neck3.weight"], f2, T3, 512, 768)
         # ---- head (models/model.yaml:65-74 and the variants headgraph.parse_head accepts), token-major
         self._head_fwd(plan, P)
 
     def _head_fwd(self, plan: Plan, P):
-        B, t = plan.B, plan.S // 4
+        B, th, tw = plan.B, plan.H // 4, plan.W // 4
         for u in self.head.units:
-            H = t >> u.level
-            M = B * H * H
+            H, W = th >> u.level, tw >> u.level
+            M = B * H * W
             tag, pname = f"h{u.k}", f"detect.{u.k}."
             plain = all(p.shr == 0 for p in u.parts) and ((u.kind == "Conv" and u.ksize == 1) or u.kind == "SPP")
             segs = []
             for ref, c, shr in u.parts:
                 src = self._ref_buf(plan, ref)
-                segs.append(SegSpec(src) if plain else SegSpec(src, c, 0, 0, 0, 1, shr, H >> shr, H >> shr))
+                segs.append(SegSpec(src) if plain else SegSpec(src, c, 0, 0, 0, 1, shr, H >> shr, W >> shr))
             if u.kind == "Conv":
                 if u.ksize == 3:
                     segs = [SegSpec(s_.t, s_.klen, 0, dy, dx, 1, s_.shr, s_.Hi, s_.Wi) for (dy, dx) in TAPS3 for s_ in segs]
-                self._conv_fwd(plan, P, tag, pname, segs, None if plain else (H, H), M, u.c1 * u.ksize ** 2, u.c2, u.ksize)
+                self._conv_fwd(plan, P, tag, pname, segs, None if plain else (H, W), M, u.c1 * u.ksize ** 2, u.c2, u.ksize)
             elif u.kind == "C3":
-                self._c3_fwd(plan, P, tag, pname, segs, (H, H), M, u.c1, u.c2)
+                self._c3_fwd(plan, P, tag, pname, segs, (H, W), M, u.c1, u.c2)
             else:
-                self._spp_fwd(plan, P, tag, pname, segs, (H, H), M, u.c1, u.c2, B)
+                self._spp_fwd(plan, P, tag, pname, segs, (H, W), M, u.c1, u.c2, B)
 
     def _ref_buf(self, plan, ref):
         """the plan buffer a headgraph.Ref names: an encoder output or a head unit's output"""
@@ -727,7 +747,8 @@ class Engine:
             if ws < 8 or 64 % ws:
                 raise NotImplementedError(f"a {H}x{W}-token stage is ONE {ws}x{ws} window (backbone_vit.py:1042-1045: no partition below "
                                           "the window size); the attention kernels walk 64-token tiles of whole window rows (window "
-                                          "side 8, 16 or 32): below S = 576 use S = 128, 256 or 512 (from 576 on every multiple of 64 runs)")
+                                          "side 8, 16 or 32): below S = 576 use S = 128, 256 or 512 (from 576 on every multiple of 64 runs); "
+                                          "an H x W input takes min(H, W) for S here")
         L2 = 2 * ws - 1
         if blk.attn.relative_position_bias_table.shape[0] != L2 * L2:
             raise ValueError(f"input resolution gives a {ws}x{ws} window but the model was built with a "
@@ -1231,7 +1252,7 @@ class Engine:
         from the masters every call).  The taps are K-segment views of the head's buffers - an Upsample / Concat entry is index
         arithmetic here too."""
         from .sr import SRBranch
-        B, t = plan.B, plan.S // 4
+        B, t = plan.B, plan.H // 4               # (square: run() refuses sr with H != W)
         br = plan.sr
         if br is None:
             names = [n for n in self.params if n.startswith("model_up.")]
@@ -1268,7 +1289,7 @@ class Engine:
 
     def _sr_extra(self, plan: Plan):
         """ref -> [(dense gradient buffer, ld, column offset, channels, shr)]: what the SR branch adds to d(feature)."""
-        B, t = plan.B, plan.S // 4
+        B, t = plan.B, plan.H // 4
         br = plan.sr
         low, deep = self.head.sr_parts
         c1 = sum(p.channels for p in low)
@@ -1302,9 +1323,8 @@ class Engine:
         if self.fused or not plan.training:
             raise RuntimeError("backward needs a training-mode, un-fused model")
         P = self._prep_for(plan.dt)
-        B, S = plan.B, plan.S
-        t = S // 4
-        T1 = B * t * t
+        B, th, tw = plan.B, plan.H // 4, plan.W // 4
+        T1 = B * th * tw
         fz = plan.fz
         fresh = self._claim_grads(None if fz is None else fz.frozen)
         if fresh:
@@ -1330,10 +1350,10 @@ class Engine:
                     wg, wn, bn = ud.any_wgrad, self.det_name + "m.0.weight", self.det_name + "m.0.bias"
                     hx = plan.bufs[self.head.by_row[self.head.head_out[0]].out_name]
                     if not ops.detect_bwd(dpred, hx, P["w"][wn], dyd, self.g[wn] if wg else None, self.g[bn] if wg else None,
-                                          B, t * t, self.na, self.no, cd, lddw=cd):
+                                          B, th * tw, self.na, self.no, cd, lddw=cd):
                         # refused (a dpred off its alignment): the three launches it replaces, live and with the same outputs
                         dzd = plan.buf("g.dzd", (T1, self.det_np))
-                        ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
+                        ops.detect_unpermute(dpred, dzd, self.det_np, B, th * tw, self.na, self.no)
                         if wg:
                             ops.gemm_tn(dzd, [SegSpec(hx)], self.g[wn], T1, self.na * self.no, cd, ldy=self.det_np, lddw=cd, dbias=self.g[bn])
                         if dyd is not None:
@@ -1343,7 +1363,7 @@ class Engine:
                 if dpred is None:                            # SR-only loss
                     ops.zero_(dzd)
                 else:
-                    ops.detect_unpermute(dpred, dzd, self.det_np, B, t * t, self.na, self.no)
+                    ops.detect_unpermute(dpred, dzd, self.det_np, B, th * tw, self.na, self.no)
         if self.sr:
             self._sr_backward(plan, dsr)             # live too: its input gradients land in plan.sr's buffers
         overlap = False
@@ -1390,20 +1410,28 @@ class Engine:
 
     def _frontend_bwd(self, plan: Plan, P, x_rgb, x_ir):
         # (3) front end: live
-        B, S = plan.B, plan.S
-        t = S // 4
+        B, H, W = plan.B, plan.H, plan.W
         fe = P["fe"]
         cb = self.model.image_encoder.chan_block
         ca_ws, ca_shift = int(cb.window_size), int(cb.shift_size)
+        irs = x_ir.shape[1] * H * W
+        gw, gb, gg, gbe, dx0 = self.g_fe_w, self.g_fe_b, self.g_fe_g, self.g_fe_be, plan.bufs["g.dx0"]
         if ca_ws == 1:
-            ws = plan.buf("fe.ws", (ops.frontend_bwd_workspace_bytes(B, S) // 4,), torch.float32)
-            ops.frontend_bwd(x_rgb, x_ir, x_ir.shape[1] * S * S, fe["w"], fe["b"], fe["g"], fe["be"], plan.bufs["g.dx0"],
-                             self.g_fe_w, self.g_fe_b, self.g_fe_g, self.g_fe_be, B, S, 1, ws)
+            if H == W:
+                ws = plan.buf("fe.ws", (ops.frontend_bwd_workspace_bytes(B, H) // 4,), torch.float32)
+                ops.frontend_bwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], dx0, gw, gb, gg, gbe, B, H, 1, ws)
+            else:
+                ws = plan.buf("fe.ws", (ops.frontend_bwd_hw_workspace_bytes(B, H, W) // 4,), torch.float32)
+                ops.frontend_bwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], dx0, gw, gb, gg, gbe, B, H, W, 1, ws)
         else:
-            de = plan.buf("fe.de", (B * t * t, 192), torch.float32)
+            de = plan.buf("fe.de", (B * (H // 4) * (W // 4), 192), torch.float32)
             ops.zero_(de)
-            ops.cross_attn_ln_bwd(plan.bufs["fe.e"], fe["g"], plan.bufs["g.dx0"], de, self.g_fe_g, self.g_fe_be, B, S, ca_ws, ca_shift)
-            ops.patch_embed4_bwd(x_rgb, x_ir, x_ir.shape[1] * S * S, de, self.g_fe_w, self.g_fe_b, B, S)
+            if H == W:
+                ops.cross_attn_ln_bwd(plan.bufs["fe.e"], fe["g"], dx0, de, gg, gbe, B, H, ca_ws, ca_shift)
+                ops.patch_embed4_bwd(x_rgb, x_ir, irs, de, gw, gb, B, H)
+            else:
+                ops.cross_attn_ln_bwd_hw(plan.bufs["fe.e"], fe["g"], dx0, de, gg, gbe, B, H, W, ca_ws, ca_shift)
+                ops.patch_embed4_bwd_hw(x_rgb, x_ir, irs, de, gw, gb, B, H, W)
 
     def _zero_frozen(self, plan: Plan, lo, hi):
         """Frozen parameters' slices in [lo, hi) of the flat buffer that a launch fusing dX with parameter gradients may have
@@ -1422,14 +1450,12 @@ class Engine:
             plan.bwd_marks.append((ops.recorded_count(), lo, hi))
 
     def _backward_main(self, plan: Plan, P):
-        B, S = plan.B, plan.S
-        t = S // 4
+        B, th, tw = plan.B, plan.H // 4, plan.W // 4
         wT, g, b = P["wT"], self.g, plan.bufs
         enc = self.model.image_encoder
         U, T = plan.unit, plan.trainable
         ops.zero_(plan.zpool("b"))                   # BN-backward reduction accumulators of every head conv
-        T1, T2, T3 = B * t * t, B * (t // 2) ** 2, B * (t // 4) ** 2
-        h2, h4 = t // 2, t // 4
+        T1, T2, T3 = B * th * tw, B * (th // 2) * (tw // 2), B * (th // 4) * (tw // 4)
         # ---- Detect
         hu = self.head.by_row[self.head.head_out[0]]
         cd = self.head.head_out[1]
@@ -1451,8 +1477,8 @@ class Engine:
         #      whose output needs no gradient is passed over; an input that needs none gets no slice (and no gather_sum_rows)
         extra = self._sr_extra(plan) if self.sr and U("model_up").runs_bwd and U("model_up").any_dx else {}
         for u in reversed(self.head.units):
-            H = t >> u.level
-            M = B * H * H
+            H, W = th >> u.level, tw >> u.level
+            M = B * H * W
             tag = f"h{u.k}"
             ur = U(tag)
             if not ur.runs_bwd:
@@ -1468,8 +1494,8 @@ class Engine:
                     if u.ksize == 1:
                         ops.gemm_nt([SegSpec(dz)], w_, din, M, u.c1, u.c2)
                     else:
-                        segs = [SegSpec(dz, u.c2, 0, -dy_, -dx_, 1, 0, H, H) for (dy_, dx_) in TAPS3]
-                        ops.gemm_nt(segs, w_, din, M, u.c1, 9 * u.c2, spatial=(H, H))
+                        segs = [SegSpec(dz, u.c2, 0, -dy_, -dx_, 1, 0, H, W) for (dy_, dx_) in TAPS3]
+                        ops.gemm_nt(segs, w_, din, M, u.c1, 9 * u.c2, spatial=(H, W))
             elif u.kind == "C3":
                 din = self._c3_bwd(plan, P, tag, dy, ld, off)
             else:
@@ -1481,9 +1507,9 @@ class Engine:
                 elif shr == 0:
                     gout[ref] = (din, u.c1, coff)
                 else:
-                    Hs = H >> shr
-                    dsrc = plan.buf(f"{tag}.dup{coff}", (B * Hs * Hs, c))
-                    ops.gather_sum_rows(din, u.c1, dsrc, c, B, Hs, Hs, shr, c, d_off=coff)
+                    Hs, Ws = H >> shr, W >> shr
+                    dsrc = plan.buf(f"{tag}.dup{coff}", (B * Hs * Ws, c))
+                    ops.gather_sum_rows(din, u.c1, dsrc, c, B, Hs, Ws, shr, c, d_off=coff)
                     gout[ref] = (dsrc, c, 0)
                 coff += c
         for j in range(3):
@@ -1551,7 +1577,7 @@ class Engine:
             # ---- patch_embed 1x1 + pos_embed
             if U("embed").runs_bwd:
                 if plan.saved["use_pos"] and T(E + "pos_embed"):
-                    ops.batch_sum(cur, g[E + "pos_embed"], B, t * t * 192)
+                    ops.batch_sum(cur, g[E + "pos_embed"], B, th * tw * 192)
                 dx0 = plan.buf("g.dx0", (T1, 192)) if U("embed").any_dx else None
                 self._linear_bwd(P, E + "patch_embed.proj", cur, b["x0"], dx0, T1, 192, 192, plan=plan, need_dx=U("embed").any_dx)
         self._zero_frozen(plan, self.fe_end, self.ddp_split)

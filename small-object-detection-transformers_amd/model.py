@@ -465,28 +465,47 @@ class Model(nn.Module):
         d["_engine"] = None
         return d
 
-    def runs_at(self, S: int) -> bool:
-        """Whether the engine runs a square S x S input on this model: the answer ``multi_scale_size`` needs before it draws a
-        size (Train.py:396-402).  Pure host code - no device, no engine - restating what ``Engine.run``, ``Engine._block_geo`` and
-        ``Engine._block_route`` refuse (tests/test_multiscale_gpu.py holds the two together): S is a multiple of 32; a stage
-        no larger than its window is ONE window, of side 8, 16 or 32 (the attention kernels walk 64-token tiles of whole window
-        rows); the window matches the block's relative-position bias table; and a stage that is not a multiple of its window
-        is zero-padded for unshifted blocks only - or, with ``pad_shifted_blocks`` set, for shifted blocks of 8-token windows too.
+    def runs_at(self, S) -> bool:
+        """Whether the engine runs an input of this size on this model: S is the side of a square input or (H, W), and
+        ``runs_at((S, S)) == runs_at(S)``.  The answer ``multi_scale_size`` needs before it draws a size (Train.py:396-402), and a
+        ``--rect`` loader before it fixes a batch shape.  Pure host code - no device, no engine - restating what ``Engine.run``,
+        ``Engine._block_geo`` and ``Engine._block_route`` refuse (tests/test_multiscale_gpu.py and tests/test_rect_gpu.py hold the
+        two together): both sides are multiples of 32; a stage whose SHORTER side is no larger than its window is ONE window of
+        that side, 8, 16 or 32 tokens (the attention kernels walk 64-token tiles of whole window rows); the window matches the
+        block's relative-position bias table; a stage side that is not a multiple of the window is zero-padded for unshifted
+        blocks only - or, with ``pad_shifted_blocks`` set, for shifted blocks of 8-token windows too; and an input whose token
+        rows match ``pos_embed`` while its columns do not is refused (the reference adds the table on the rows alone and cannot
+        broadcast it, backbone_vit.py:215-217).  The super-resolution branch (``sr=True``) runs square inputs only.
         For a model built at 512 or 1024: S = 512 and every multiple of 64 from 576; with the switch on 512, 544 and every
-        multiple of 32 from 576."""
-        if isinstance(S, bool) or not isinstance(S, int) or S <= 0 or S % 32:
-            return False
+        multiple of 32 from 576; H x W with both sides from that list, but for the pos_embed case.  A model built at 256 runs
+        H x 256 with H a multiple of 64 above 256 (stage 3 is one 16-token window across, zero-padded along H) and, as
+        multiples of 32 go, those its stage 2 can pad.  Every other argument - not an int or a 2-sequence of positive ints -
+        returns False."""
+        if isinstance(S, (tuple, list)):
+            if len(S) != 2:
+                return False
+            H, W = S
+        else:
+            H = W = S
+        for v in (H, W):
+            if isinstance(v, bool) or not isinstance(v, int) or v <= 0 or v % 32:
+                return False
         enc = self.image_encoder
-        for stage, H in ((enc.stage1, S // 4), (enc.stage2, S // 8), (enc.stage3, S // 16)):
+        pt = enc.pos_embed.shape[1]
+        if H // 4 == pt and W // 4 != pt:
+            return False
+        if H != W and getattr(self, "sr", False):
+            return False
+        for stage, (h, w) in ((enc.stage1, (H // 4, W // 4)), (enc.stage2, (H // 8, W // 8)), (enc.stage3, (H // 16, W // 16))):
             for blk in stage:
                 ws, shift = blk.window_size, blk.shift_size
-                if H <= ws:
-                    ws, shift = H, 0
+                if min(h, w) <= ws:
+                    ws, shift = min(h, w), 0
                     if ws < 8 or 64 % ws:
                         return False
                 if blk.attn.relative_position_bias_table.shape[0] != (2 * ws - 1) ** 2:
                     return False
-                if H % ws and shift > 0 and not (getattr(self, "pad_shifted_blocks", False) and ws == 8):
+                if (h % ws or w % ws) and shift > 0 and not (getattr(self, "pad_shifted_blocks", False) and ws == 8):
                     return False
         return True
 

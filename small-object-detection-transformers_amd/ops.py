@@ -485,6 +485,23 @@ def frontend_bwd(rgb, ir_plane, ir_bstride, w, b, gamma, beta, dout, dw, db, dga
             dt_code(dout))
 
 
+def frontend_fwd_hw(rgb, ir_plane, ir_bstride, w, b, gamma, beta, out, B, H, W, ca_ws=1):
+    """sodt_frontend_fwd on an H x W image: out is [B * (H/4) * (W/4)][192], row (b * H/4 + y) * W/4 + x."""
+    _launch("sodt_frontend_fwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(out),
+            B, H, W, ca_ws, dt_code(out))
+
+
+def frontend_bwd_hw_workspace_bytes(B: int, H: int, W: int) -> int:
+    return int(_lib.sodt_frontend_bwd_hw_workspace_bytes(B, H, W))
+
+
+def frontend_bwd_hw(rgb, ir_plane, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, H, W, ca_ws=1, ws=None):
+    """``ws``: f32 scratch of ``frontend_bwd_hw_workspace_bytes`` (two-stage reduction); None = direct atomics."""
+    _launch("sodt_frontend_bwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(dout),
+            _p(dw), _p(db), _p(dgamma), _p(dbeta), B, H, W, ca_ws, _p(ws), 0 if ws is None else ws.numel() * ws.element_size(),
+            dt_code(dout))
+
+
 def patch_embed4_fwd(rgb, ir_plane, ir_bstride, w, b, e, B, S):
     _launch("sodt_patch_embed4_fwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(e), B, S)
 
@@ -499,6 +516,22 @@ def cross_attn_ln_fwd(e, gamma, beta, out, B, S, ws, shift):
 
 def cross_attn_ln_bwd(e, gamma, dout, de, dgamma, dbeta, B, S, ws, shift):
     _launch("sodt_cross_attn_ln_bwd", _p(e), _p(gamma), _p(dout), _p(de), _p(dgamma), _p(dbeta), B, S, ws, shift, dt_code(dout))
+
+
+def patch_embed4_fwd_hw(rgb, ir_plane, ir_bstride, w, b, e, B, H, W):
+    _launch("sodt_patch_embed4_fwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(e), B, H, W)
+
+
+def patch_embed4_bwd_hw(rgb, ir_plane, ir_bstride, de, dw, db, B, H, W):
+    _launch("sodt_patch_embed4_bwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(de), _p(dw), _p(db), B, H, W)
+
+
+def cross_attn_ln_fwd_hw(e, gamma, beta, out, B, H, W, ws, shift):
+    _launch("sodt_cross_attn_ln_fwd_hw", _p(e), _p(gamma), _p(beta), _p(out), B, H, W, ws, shift, dt_code(out))
+
+
+def cross_attn_ln_bwd_hw(e, gamma, dout, de, dgamma, dbeta, B, H, W, ws, shift):
+    _launch("sodt_cross_attn_ln_bwd_hw", _p(e), _p(gamma), _p(dout), _p(de), _p(dgamma), _p(dbeta), B, H, W, ws, shift, dt_code(dout))
 
 
 def bn_finalize(stats, mean_rstd, running_mean, running_var, count, Cc, eps, momentum):
