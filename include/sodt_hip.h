@@ -501,6 +501,31 @@ int sodt_nms_select(const float* z, int nc, const unsigned long long* keys, long
                     int agnostic, void* ws, size_t ws_bytes, float* out, int* out_index, int* out_count,
                     sodt_stream_t st);
 
+/* ---- non_max_suppression (general.py:425-512), a whole batch per call, no host read, eval only ---------------
+ * The batched sibling of the three entries above: the same candidates, the same 64-bit key, the same result per image.
+ * z: decoded rows (B, N, 5+nc) f32.  labels / nlab / lab_cap (all null / 0, or all set): the autolabelling rows of
+ *   general.py:451-458, labels (B, lab_cap, 5) f32 [cls x y w h] of which image b uses the first nlab[b] (device int32,
+ *   clamped to lab_cap); they are candidates' rows N + k with obj = 1 and a one-hot class, read in place - no
+ *   concatenated prediction exists.  A label whose class is not in [0, nc) has no class score.
+ * conf_thres / iou_thres / multi_label (forced off when nc == 1) / class_allow (nc bytes, device, nullable) / agnostic:
+ *   as sodt_nms_candidates and sodt_nms_select (general.py:425-512).
+ * Per image: candidates into a key segment of rows * (multi_label ? nc : 1) slots (rows = N + lab_cap), ONE segmented
+ *   radix sort (descending score, ties in the reference's candidate order), the first 30000 survive (general.py:489-490),
+ *   greedy class-offset NMS that stops at 300 kept (torchvision.ops.nms then i[:max_det], general.py:493-498), merge-NMS
+ *   and the redundancy filter where 1 < candidates < 3000 (general.py:499-506).
+ * out_rows: (B*300, 6) f32 [x1 y1 x2 y2 conf cls], image b's rows at [out_off[b], out_off[b+1]); out_index: (B*300) int32,
+ *   the candidate id row*nc + class of each row; out_off: (B+1) int32, written on the device.  Rows and ids from
+ *   out_off[B] to B*300 are zeros.  This is the packed (det, det_off) form of sodt_eval_match / sodt_confusion_update with
+ *   n_det = B*300 as the upper bound.
+ * ws: 16-byte aligned scratch of at least sodt_nms_batch_workspace_bytes(B, N + lab_cap, nc, multi_label): a function
+ *   of these host-known arguments alone.  B <= 4096, rows * nc and B * slots below 2^31.
+ * Neither entry allocates, synchronises or reads device memory on the host; arguments are checked before the first
+ *   launch (SODT_EINVAL, nothing written); the launches are the same for every B and every count. */
+int sodt_nms_batch_workspace_bytes(int B, long rows, int nc, int multi_label, size_t* bytes);
+int sodt_nms_batch(const float* z, int B, int N, int nc, const float* labels, const int* nlab, int lab_cap,
+                   float conf_thres, float iou_thres, int multi_label, const unsigned char* class_allow, int agnostic,
+                   void* ws, size_t ws_bytes, float* out_rows, int* out_index, int* out_off, sodt_stream_t st);
+
 /* ---- weighted boxes fusion (general.py:515-563, ensemble_boxes/ensemble_boxes_wbf.py), a batch per call, eval only ----
  * sodt_wbf_candidates: general.py:523-544 for all B images in one launch.  z: (B, N, 5+nc) f32.  Keeps rows with
  *   obj > conf_thres whose best class (first maximum of the f32 product obj * cls) has obj * cls > conf_thres, divides

@@ -124,6 +124,9 @@ SIGNATURES = {
     "sodt_nms_candidates": [_P, _I, _I, C.c_float, _I, _P, _P, _I, _P, _P],
     "sodt_nms_workspace_bytes": [_L, C.POINTER(C.c_size_t)],
     "sodt_nms_select": [_P, _I, _P, _L, C.c_float, _I, _P, C.c_size_t, _P, _P, _P, _P],
+    # general.py:425-512 for a whole batch (csrc/nms_batch.hip)
+    "sodt_nms_batch_workspace_bytes": [_I, _L, _I, _I, C.POINTER(C.c_size_t)],
+    "sodt_nms_batch": [_P, _I, _I, _I, _P, _P, _I, _F, _F, _I, _P, _I, _P, C.c_size_t, _P, _P, _P, _P],
     "sodt_wbf_candidates": [_P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "sodt_wbf_fuse_workspace_bytes": [_I, _L, C.POINTER(C.c_size_t)],
     "sodt_wbf_fuse": [_P, _P, _P, _P, _P, _P, _I, _L, C.POINTER(C.c_double), _I, C.c_double, _F, _I, _I, _I, _P, C.c_size_t,

@@ -22,7 +22,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # Per-source overrides, appended after FLAGS (the last -ffp-contract wins).  With -ffp-contract=fast the backend fuses
 # multiply-adds whatever `#pragma clang fp contract(off)` says, so a file that must reproduce the reference's rounding
 # bit for bit is compiled with contraction off.
-SOURCE_FLAGS = {"metrics.hip": ["-ffp-contract=off"], "wbf.hip": ["-ffp-contract=off"], "autoanchor.hip": ["-ffp-contract=off"]}
+SOURCE_FLAGS = {"metrics.hip": ["-ffp-contract=off"], "wbf.hip": ["-ffp-contract=off"], "autoanchor.hip": ["-ffp-contract=off"],
+                "nms_batch.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

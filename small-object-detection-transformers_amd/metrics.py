@@ -7,7 +7,8 @@ Everything after NMS runs in HIP kernels (csrc/metrics.hip) behind the C ABI (`s
 appends to device buffers without synchronising (non_max_suppression has already read the per-image counts, so
 packing the batch needs no device read); `compute()` runs ap_per_class on the device and synchronises once.
 `ConfusionMatrix.update` / `.process_batch` add into a device matrix the same way; `.matrix` synchronises once.
-torch only allocates and packs here.
+torch only allocates and packs here.  Both `update`s also take the `BatchDetections` of `non_max_suppression_batch` in
+place of the list: its packed rows and device offsets go to the same entries as they are, with no host read at all.
 
 Differences from the reference, documented in DESIGN.md:
   * predictions with equal confidence keep their row order (a stable sort); the reference's np.argsort(-conf) is
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .nms import BatchDetections
 
 NIOU = 10
 MAX_CLASSES = 4096
@@ -139,10 +141,12 @@ class DetectionMetrics:
     def reset(self) -> None:
         self.seen = 0
         self._correct, self._det, self._tcls = [], [], []
+        self._used = []         # per batch: None (list input, every row used) or the device int32[1] count of used rows
 
-    def update(self, out: Sequence[torch.Tensor], targets: torch.Tensor, img_hw, shapes) -> None:
-        """out: non_max_suppression's list ((n_i, 6) per image); targets (nt, 6) [img cls x y w h] in input pixels;
-        img_hw = img.shape[2:]; shapes: the loader's per-image ((h0, w0), ((gain_h, gain_w), (padw, padh)) or None)."""
+    def update(self, out, targets: torch.Tensor, img_hw, shapes) -> None:
+        """out: non_max_suppression's list ((n_i, 6) per image) or non_max_suppression_batch's BatchDetections; targets
+        (nt, 6) [img cls x y w h] in input pixels; img_hw = img.shape[2:]; shapes: the loader's per-image
+        ((h0, w0), ((gain_h, gain_w), (padw, padh)) or None)."""
         B = len(out)
         if len(shapes) != B:
             raise ValueError(f"{len(shapes)} shapes for {B} images")
@@ -150,16 +154,26 @@ class DetectionMetrics:
         if B == 0:
             return
         dev = self.device
+        if isinstance(out, BatchDetections):     # packed on the device already: B * 300 rows, of which offsets[B] are used
+            self._match(out.rows, out.offsets, targets, img_hw, shapes, out.offsets[B:B + 1])
+            return
         counts = [int(o.shape[0]) for o in out]
         off = np.zeros(B + 1, dtype=np.int32)
         np.cumsum(counts, out=off[1:])
         n_det = int(off[-1])
         det = (torch.cat([o.detach().to(dev, torch.float32).view(-1, 6) for o in out]) if n_det
                else torch.zeros((0, 6), dtype=torch.float32, device=dev)).contiguous()
+        off_d = torch.from_numpy(off).pin_memory().to(dev, non_blocking=True)
+        self._match(det, off_d, targets, img_hw, shapes, None)
+
+    def _match(self, det, off_d, targets, img_hw, shapes, used) -> None:
+        """One sodt_eval_match over det (n_det, 6) / off_d (B+1); `used`: see reset().  With a BatchDetections n_det is
+        the upper bound B * 300 and the entry clamps to the offsets; the rows of `correct` it never writes are cut off in
+        _packed(), where the host reads the device anyway."""
+        dev = self.device
+        B, n_det = off_d.numel() - 1, det.shape[0]
         tg = targets.detach().to(dev, torch.float32).reshape(-1, 6).contiguous()
-        off_h = torch.from_numpy(off).pin_memory()
         geom_h = torch.tensor([_geometry(img_hw, s) for s in shapes], dtype=torch.float32).pin_memory()
-        off_d = off_h.to(dev, non_blocking=True)
         geom_d = geom_h.to(dev, non_blocking=True)
         correct = torch.empty((n_det, NIOU), dtype=torch.uint8, device=dev)
         tcls = torch.empty(tg.shape[0], dtype=torch.float32, device=dev)
@@ -169,14 +183,22 @@ class DetectionMetrics:
         self._correct.append(correct)
         self._det.append(det)
         self._tcls.append(tcls)
+        self._used.append(used)
 
     def _packed(self):
         dev = self.device
         if not self._det:
             return (torch.zeros((0, NIOU), dtype=torch.uint8, device=dev), torch.zeros(0, device=dev),
                     torch.zeros(0, device=dev), torch.zeros(0, device=dev))
-        det = torch.cat(self._det)
-        return torch.cat(self._correct), det[:, 4].contiguous(), det[:, 5].contiguous(), torch.cat(self._tcls)
+        dets, corrects = self._det, self._correct
+        batched = [i for i, u in enumerate(self._used) if u is not None]
+        if batched:             # drop the unused (zero / never written) rows of the batched updates: one host read for all
+            used = torch.cat([self._used[i] for i in batched]).tolist()
+            dets, corrects = list(dets), list(corrects)
+            for i, n in zip(batched, used):
+                dets[i], corrects[i] = dets[i][:n], corrects[i][:n]
+        det = torch.cat(dets)
+        return torch.cat(corrects), det[:, 4].contiguous(), det[:, 5].contiguous(), torch.cat(self._tcls)
 
     def stats(self):
         """The reference's `stats` after test.py:255: numpy (correct bool (n, 10), conf f32, pcls f32, tcls f64)."""
@@ -250,8 +272,9 @@ class ConfusionMatrix:
         tg = torch.cat([torch.zeros((lab.shape[0], 1), dtype=torch.float32, device=dev), lab], 1).contiguous()
         self._launch(det, off, tg, None)
 
-    def update(self, out: Sequence[torch.Tensor], targets: torch.Tensor, img_hw, shapes) -> None:
-        """process_batch for every image of a batch in one launch sequence; the arguments of DetectionMetrics.update.
+    def update(self, out, targets: torch.Tensor, img_hw, shapes) -> None:
+        """process_batch for every image of a batch in one launch sequence; the arguments of DetectionMetrics.update
+        (the NMS list or a BatchDetections, whose rows and device offsets are used as they are).
         Images without detections count their labels as missed (what process_batch does when it is given none)."""
         B = len(out)
         if len(shapes) != B:
@@ -259,7 +282,7 @@ class ConfusionMatrix:
         if B == 0:
             return
         dev = self.device
-        det, off = _pack(out, dev)
+        det, off = (out.rows, out.offsets) if isinstance(out, BatchDetections) else _pack(out, dev)
         tg = targets.detach().to(dev, torch.float32).reshape(-1, 6).contiguous()
         geom = torch.tensor([_geometry(img_hw, s) for s in shapes], dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
         self._launch(det, off, tg, geom)

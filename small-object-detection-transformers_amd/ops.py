@@ -672,6 +672,26 @@ def nms_select(z_img, keys, n_total, iou_thres, agnostic, ws, out, out_index, ou
             int(bool(agnostic)), _p(ws), ws.numel() * ws.element_size(), _p(out), _p(out_index), _p(out_count))
 
 
+def nms_batch_workspace_bytes(B: int, rows: int, nc: int, multi_label) -> int:
+    """Scratch bytes of nms_batch (general.py:425-512 for a batch): a function of B, rows = N + lab_cap, nc, multi_label."""
+    b = C.c_size_t(0)
+    rc = _lib.sodt_nms_batch_workspace_bytes(int(B), int(rows), int(nc), int(bool(multi_label)), C.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"sodt_nms_batch_workspace_bytes failed with status {rc} (B <= 4096, B * rows * nc < 2^31)")
+    return int(b.value)
+
+
+def nms_batch(z, labels, nlab, conf_thres, iou_thres, multi_label, class_allow, agnostic, ws, out_rows, out_index, out_off):
+    """non_max_suppression of general.py:425-512 for all B images of z (B, N, 5+nc) in one launch sequence without a host
+    read.  labels (B, lab_cap, 5) f32 / nlab (B) int32 or None: the autolabelling rows.  out_rows (B*300, 6) f32,
+    out_index (B*300) int32, out_off (B+1) int32: the packed form eval_match / confusion_update take."""
+    B, N, no = z.shape
+    lab_cap = 0 if labels is None else labels.shape[1]
+    _launch("sodt_nms_batch", _p(z), B, N, no - 5, _p(labels), _p(nlab), lab_cap, C.c_float(conf_thres),
+            C.c_float(iou_thres), int(bool(multi_label)), _p(class_allow), int(bool(agnostic)), _p(ws),
+            ws.numel() * ws.element_size(), _p(out_rows), _p(out_index), _p(out_off))
+
+
 def wbf_candidates(z, conf_thres, image_size, boxes, scores, labels, src, counts):
     """z (B, N, 5+nc) f32 -> per-image compact candidates + device counts (general.py:523-544)."""
     B, N, no = z.shape
