@@ -450,6 +450,41 @@ int sodt_detect_unpermute(const float* dpred, void* dz, int ldz, int B, int HW, 
 int sodt_detect_decode(const float* raw, const float* anchor_grid, float* z, int B, int na, int ny, int nx,
                        int no, float stride, sodt_stream_t st);
 
+/* Test-time augmentation (csrc/tta.hip; basics/models/model.py:155-184, the `--augment` of basics/test.py).
+ *
+ * sodt_tta_scale makes every augmented input of one call in ONE launch.  Per pass it replaces, for the RGB and the IR batch,
+ * `x.flip(fi)` (model.py:161-162), `F.interpolate(img, size=(int(h * ratio), int(w * ratio)), mode='bilinear',
+ * align_corners=False)` and `F.pad(img, [0, Wp - w, 0, Hp - h], value=0.447)` (torch_utils.py:254-259).  rgb / ir: f32
+ * (B, c, H, W) contiguous (device); c_ir may be 0 (ir and every out_ir then unused).  passes: a HOST table of npass <=
+ * SODT_TTA_MAX_PASSES entries that travels to the kernel by value: out_rgb / out_ir f32 (B, c, Hp, Wp); (h, w) the content size
+ * the input is resized to, (Hp, Wp) >= (h, w) the padded size; flip 0, 2 (up-down) or 3 (left-right), applied to the source
+ * coordinate, i.e. before the resize.  Source index and blend weight come from the exact integer quotient and remainder of
+ * max((2 o + 1) * in - out, 0) / (2 * out); every output element is written, the pixels outside (h, w) as 0.447f; (h, w) ==
+ * (H, W) is the flipped copy bit for bit.
+ * SODT_EINVAL, nothing launched: a null pointer, a non-positive size, batch or c_rgb (c_ir < 0), h > Hp or w > Wp, a flip
+ * outside {0, 2, 3}, npass outside 1 .. SODT_TTA_MAX_PASSES, or one of H * W, 2 * h * H, 2 * w * W reaching 2^31. */
+#define SODT_TTA_MAX_PASSES 4
+typedef struct {
+  float* out_rgb; float* out_ir;
+  int h, w;                  /* content size */
+  int Hp, Wp;                /* padded size */
+  int flip;                  /* 0, 2 = up-down, 3 = left-right */
+} sodt_tta_pass;
+int sodt_tta_scale(const float* rgb, const float* ir, int B, int c_rgb, int c_ir, int H, int W, const sodt_tta_pass* passes,
+                   int npass, sodt_stream_t st);
+
+/* sodt_detect_decode for one pass of the augmented forward, written into its slice of the concatenated output with the
+ * de-scale and the de-flip of model.py:178-182 applied: rows row_off .. row_off + na*ny*nx of z f32 (B, rows_total, no) get the
+ * decoded values (the same arithmetic as sodt_detect_decode, shared source), columns 0..3 divided by si (IEEE f32 division,
+ * what `yi[..., :4] /= si` is on ATen's CPU path), then x = (float)img_w - x for flip 3, y = (float)img_h - y for flip 2
+ * (img_h, img_w: the ORIGINAL input's size).  Rows outside the slice are not touched.
+ * SODT_EINVAL, nothing launched: what sodt_detect_decode refuses, row_off < 0, a slice that ends past rows_total, si not a
+ * positive finite number, a flip outside {0, 2, 3}, a non-positive img_h or img_w, na * ny * nx * no reaching 2^31 (the index
+ * inside one image is 32-bit), B > 65535. */
+int sodt_detect_decode_tta(const float* raw, const float* anchor_grid, float* z, int B, int na, int ny, int nx, int no,
+                           float stride, long row_off, long rows_total, float si, int flip, int img_h, int img_w,
+                           sodt_stream_t st);
+
 /* The Detect level in one pass each way (csrc/detect.hip; model.py:44-58 and its autograd), bf16 only.  M = B * HW rows, N = na * no:
  *   sodt_detect_fwd   pred[b][a][p][o] (f32) = X[b*HW + p][0:K] . W[a*no + o][0:K] + bias[a*no + o]  - what sodt_gemm_nt computes
  *                     with SODT_EPI_DETECT | SODT_EPI_BIAS (same products, same K order), written as whole runs of pred

@@ -105,6 +105,15 @@ class StepCtl(C.Structure):
                 ("reserved", C.c_int * 2)]
 
 
+TTA_MAX_PASSES = 4                                    # SODT_TTA_MAX_PASSES
+
+
+class TtaPass(C.Structure):
+    """sodt_tta_pass (include/sodt_hip.h): one augmented input pair of sodt_tta_scale."""
+    _fields_ = [("out_rgb", C.c_void_p), ("out_ir", C.c_void_p), ("h", C.c_int), ("w", C.c_int),
+                ("Hp", C.c_int), ("Wp", C.c_int), ("flip", C.c_int)]
+
+
 class PrepDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p),
                 ("d0", C.c_int), ("d1", C.c_int), ("d2", C.c_int),
@@ -171,6 +180,9 @@ SIGNATURES = {
     "sodt_gather_sum_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_detect_unpermute": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_detect_decode": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    # basics/models/model.py:155-184 (csrc/tta.hip)
+    "sodt_tta_scale": [_P, _P, _I, _I, _I, _I, _I, C.POINTER(TtaPass), _I, _P],
+    "sodt_detect_decode_tta": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _L, _L, _F, _I, _I, _I, _P],
     "sodt_detect_fwd": [C.POINTER(DetectArgs), _I, _P],
     "sodt_detect_bwd": [C.POINTER(DetectArgs), _I, _P],
     "sodt_prep_weights": [_P, _I, _I, _I, _P],

@@ -4,6 +4,7 @@
 //   Concat slot copies (models/model.yaml:66-72), Detect's permutes and eval decode
 //   (model.py:55-64), parameter preparation.  All token-major, 16-byte accesses.
 #include "common.h"
+#include "detect_decode.h"
 #include "launch.h"
 #include "../../include/sodt_hip.h"
 
@@ -340,13 +341,7 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(const float* __restr
     const int x = (int)(r % nx); r /= nx;
     const int y = (int)(r % ny); r /= ny;
     const int a = (int)(r % na);
-    const float s = sigmoid_f(raw[i]);
-    float v = s;
-    if (o == 0) v = (s * 2.f - 0.5f + (float)x) * stride;
-    else if (o == 1) v = (s * 2.f - 0.5f + (float)y) * stride;
-    else if (o == 2) v = (s * 2.f) * (s * 2.f) * anchor_grid[a * 2];
-    else if (o == 3) v = (s * 2.f) * (s * 2.f) * anchor_grid[a * 2 + 1];
-    zout[i] = v;   // (B, na, ny, nx, no) flat == (B, na*ny*nx, no)
+    zout[i] = detect_decode_value(raw[i], o, x, y, a, anchor_grid, stride);   // (B, na, ny, nx, no) flat == (B, na*ny*nx, no)
   }
 }
 

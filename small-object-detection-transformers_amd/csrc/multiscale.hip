@@ -18,6 +18,7 @@
 // stage shrinks by more than four in area an output pixel's four stage-1 values cost less than the patch under it (and
 // under a long enough shrink no patch fits the LDS): such launches skip the patch and form the four values per pixel.
 #include "common.h"
+#include "bilinear.h"
 #include "launch.h"
 #include "../../include/sodt_hip.h"
 
@@ -51,14 +52,7 @@ __device__ __forceinline__ void ms_coord1(int o, int in, int mid, int& i0, float
   l = (float)(n - i0 * d) / (float)d;
 }
 
-// stage 2, align_corners=False: intermediate index and weight of output index o (mid -> out pixels)
-__device__ __forceinline__ void ms_coord2(int o, int mid, int out, int& i0, float& l) {
-  const int d = 2 * out;
-  int n = (2 * o + 1) * mid - out;
-  n = n > 0 ? n : 0;
-  i0 = n / d;
-  l = (float)(n - i0 * d) / (float)d;
-}
+// stage 2, align_corners=False: ms_coord2 of bilinear.h (mid -> out pixels)
 
 // the stage-1 value at rows (y0, y1, ly), columns (x0, x1, lx) of one uint8 plane
 __device__ __forceinline__ float ms_value1(const unsigned char* sp, int Win, int y0, int y1, float ly, int x0, int x1, float lx) {
@@ -75,14 +69,6 @@ __device__ __forceinline__ float ms_value1_at(const unsigned char* sp, const MsA
   ms_coord1(ym, a.Hin, a.Hmid, y0, ly);
   ms_coord1(xm, a.Win, a.Wmid, x0, lx);
   return ms_value1(sp, a.Win, y0, y0 + 1 < a.Hin ? y0 + 1 : a.Hin - 1, ly, x0, x0 + 1 < a.Win ? x0 + 1 : a.Win - 1, lx);
-}
-
-// i = q * d + r with 0 <= r < d, for 0 <= i < 2^20 and 1 <= d <= 2^10, rcp = 1.0f / d: the estimate is off by at most one
-__device__ __forceinline__ void ms_divmod(int i, int d, float rcp, int& q, int& r) {
-  q = (int)((float)i * rcp);
-  r = i - q * d;
-  if (r < 0) { q -= 1; r += d; }
-  if (r >= d) { q += 1; r -= d; }
 }
 
 __global__ __launch_bounds__(MS_THREADS) void preprocess_u8_ms_kernel(const MsArgs a) {

@@ -579,6 +579,14 @@ class Engine:
         ops.detect_decode(pred, ag, z, B, na, ny, nx, no, 4.0)
         return z
 
+    def decode_tta(self, pred, z, row_off, si, flip, img_h, img_w):
+        """decode of one pass of the augmented forward into rows row_off .. row_off + na * ny * nx of z (B, rows, no), with the
+        de-scale and de-flip of model.py:178-182; returns the row after the slice."""
+        B, na, ny, nx, no = pred.shape
+        ag = self.buffers[self.det_name + "anchor_grid"].reshape(-1).contiguous().float()
+        ops.detect_decode_tta(pred, ag, z, B, na, ny, nx, no, 4.0, row_off, si, flip, img_h, img_w)
+        return row_off + na * ny * nx
+
     def _features(self, plan):
         """y[0..10] of forward_once (model.py:246,281) as NCHW *views* of the workspace (valid until the
         next forward).  y4, y5, y8, y9 (upsample / concat) are never materialised by the kernels: the list

@@ -388,6 +388,10 @@ class Model(nn.Module):
         # True: shifted blocks whose grid is no multiple of their 8-token window run on the reference's zero padding
         # (csrc/attention_sp.hip) instead of being refused - every multiple of 32 from 576 runs, and 544.  Read at each forward.
         self.pad_shifted_blocks = False
+        # the passes of forward(augment=True) (model.py:157-158): scales in (0, 1], flips None / 2 (up-down) / 3 (left-right),
+        # equal length, at most four.  Read and validated at each augmented forward (tta.check_passes).
+        self.tta_scales = (1, 0.83, 0.67)
+        self.tta_flips = (None, 3, None)
         self._engine = None
         self._nms: Optional[NMS] = None      # set by .nms(); kept outside self.model so state_dict keys do not move
 
@@ -518,12 +522,49 @@ class Model(nn.Module):
                 self._engine.ddp = self._pending_ddp
         return self._engine
 
+    def _forward_augment(self, eng, x, ir, dt):
+        """model.py:155-184, test-time augmentation: per pass (``tta_scales``, ``tta_flips``) the input is flipped, scaled and
+        padded (``scale_img``), run through the plain eval forward, and its decoded boxes are de-scaled and de-flipped; the
+        passes are concatenated along the rows.  Returns ``(z, None)`` with z f32 (B, sum of the passes' rows, no), the
+        reference's 2-tuple - or ``(detections, None)`` with ``.nms()`` on.
+
+        Launches: ONE ``sodt_tta_scale`` for every scaled input of both modalities, then per pass the plain forward's list and one
+        ``sodt_detect_decode_tta`` that writes the pass's rows of z in place - no host read, no flip / interpolate / pad / cat.
+
+        Two things differ from the reference's text.  The padded size of a scaled copy comes from ``tta.tta_sizes``: the
+        reference's ``ceil(side * si / gs) * gs`` with ``gs = max(stride, 32)`` instead of the stride 4, moved to a size
+        ``runs_at`` accepts.  And the reference takes ``forward_once(...)[0]`` (model.py:175), which in this fork is the
+        ``(z, x)`` tuple of Detect and fails at ``yi[..., :4]``; here yi is z, what upstream's line means."""
+        from . import tta
+        scales, flips = tta.check_passes(getattr(self, "tta_scales", tta.SCALES), getattr(self, "tta_flips", tta.FLIPS))
+        if x.dim() != 4 or ir.dim() != 4:
+            raise ValueError("expected x (B,3,H,W) and ir (B,>=1,H,W)")
+        x, ir = x.float().contiguous(), ir.float().contiguous()
+        B, _, H, W = x.shape
+        det = self.detect[-1]
+        sizes = tta.tta_sizes((H, W), scales, max(int(self.stride.max()), 32), self.runs_at)
+        made = [k for k, (si, fi) in enumerate(zip(scales, flips)) if si != 1 or fi]
+        inputs = [(x, ir)] * len(scales)
+        if made:
+            for k, pair in zip(made, tta.scale_pair(x, ir, [(*sizes[k], flips[k]) for k in made])):
+                inputs[k] = pair
+        rows = sum(det.na * (hp // 4) * (wp // 4) for _, (hp, wp) in sizes)
+        z = torch.empty(B, rows, det.no, device=x.device, dtype=torch.float32)
+        off = 0
+        for (xi, iri), si, fi in zip(inputs, scales, flips):
+            pred = eng.run(xi, iri, dt, False)[0]
+            off = eng.decode_tta(pred, z, off, si, fi, H, W)        # before the next run: pred may not outlive it
+        if getattr(self, "_nms", None) is not None:
+            return self._nms((z, None)), None
+        return z, None
+
     def forward(self, x, ir=None, input_mode="RGB+IR", augment=False, profile=False):
-        """model.py:151-211.  train -> ([pred], y);  eval -> (z, [pred], y)."""
+        """model.py:151-211.  train -> ([pred], y);  eval -> (z, [pred], y);  eval with augment=True -> (z, None), see
+        ``_forward_augment``."""
         if input_mode != "RGB+IR":
             raise NotImplementedError("only input_mode='RGB+IR' (the 4-channel encoder of model.yaml) is built")
-        if augment:
-            raise NotImplementedError("TTA (augment=True) is outside the hot path")
+        if augment and (self.training or self.export):
+            raise ValueError("augment=True is an evaluation path (model.py:175 indexes the training output, a list): call .eval() first")
         if ir is None:
             raise ValueError("ir is required")
         if not x.is_cuda:
@@ -533,6 +574,8 @@ class Model(nn.Module):
         dt = self.compute_dtype
         if dt is None:
             dt = torch.bfloat16 if torch.is_autocast_enabled() else torch.float32
+        if augment:
+            return self._forward_augment(eng, x, ir, dt)
         training = self.training or self.export
         pred, feats, out_sr = eng.run(x, ir, dt, training)
         if training:

@@ -651,6 +651,24 @@ def detect_decode(raw, anchor_grid, z, B, na, ny, nx, no, stride):
     _launch("sodt_detect_decode", _p(raw), _p(anchor_grid), _p(z), B, na, ny, nx, no, C.c_float(stride))
 
 
+def tta_scale(x, ir, passes):
+    """Every augmented input of one call in one launch (model.py:161-162, torch_utils.py:249-259).  x f32 (B, c, H, W), ir the
+    same with its own channel count or None; passes: up to four (out_rgb, out_ir | None, (h, w), flip) with out_* f32
+    (B, c, Hp, Wp) - the input flipped (0, 2 = up-down, 3 = left-right), resized to (h, w) and padded with 0.447."""
+    B, c1, H, W = x.shape
+    tab = (L.TtaPass * len(passes))()
+    for t, (o1, o2, (h, w), flip) in zip(tab, passes):
+        t.out_rgb, t.out_ir, t.h, t.w, t.Hp, t.Wp, t.flip = _p(o1), _p(o2), h, w, o1.shape[2], o1.shape[3], flip
+    _launch("sodt_tta_scale", _p(x), _p(ir), B, c1, 0 if ir is None else ir.shape[1], H, W, tab, len(passes))
+
+
+def detect_decode_tta(raw, anchor_grid, z, B, na, ny, nx, no, stride, row_off, si, flip, img_h, img_w):
+    """detect_decode of one augmented pass into rows row_off .. of z (B, rows_total, no), de-scaled and de-flipped
+    (model.py:178-182)."""
+    _launch("sodt_detect_decode_tta", _p(raw), _p(anchor_grid), _p(z), B, na, ny, nx, no, C.c_float(stride), row_off,
+            z.shape[1], C.c_float(si), flip, img_h, img_w)
+
+
 def nms_candidates(z_img, conf_thres, multi_label, class_allow, keys, count):
     """z_img (N, 5+nc) f32 of one image -> sort keys + device count (general.py:433-480)."""
     N, no = z_img.shape
