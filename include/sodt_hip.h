@@ -351,54 +351,35 @@ int sodt_convmlp_decompose(const float* dweff, const float* colsum, const float*
 /* Front end (backbone_vit.py:195-210): channel split, 4x Conv2d(1->48,k4,s4) (R with
  * padding 1), pairwise cross-channel attention (R<-G, G<-B, B<-IR, IR<-G; 12 heads x 4,
  * scale 1/2, window ca_ws, no projections) + residual + LayerNorm(48), concatenated to
- * [B*t*t][192].  rgb (B,3,S,S) f32 / ir plane pointer with its batch stride, f32 in
- * [0,1].  params f32: w[4][48][16], b[4][48], gamma[4][48], beta[4][48].  ca_ws == 1
- * is the shipped configuration (backbone_vit.py:438).
+ * [B*th*tw][192], th x tw = H/4 x W/4 tokens, output row (b * th + y) * tw + x.  rgb (B,3,H,W) f32 / ir plane pointer with
+ * its batch stride, f32 in [0,1].  params f32: w[4][48][16], b[4][48], gamma[4][48], beta[4][48].  ca_ws == 1
+ * is the shipped configuration (backbone_vit.py:438).  H % 4 or W % 4 non-zero is refused (SODT_EINVAL, nothing launched):
+ * the patches are 4 x 4 and are read as 16-byte rows.
  * The backward accumulates into dw/db/dgamma/dbeta.  With a workspace of sodt_frontend_bwd_workspace_bytes() (f32, need
  * not be zeroed) the per-workgroup partial sums are reduced by a second small kernel; ws == NULL falls back to direct
  * atomics (same result up to summation order, ~0.15 ms slower at 8 x 1024^2). */
 int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                      const float* gamma, const float* beta, void* out, int B, int S, int ca_ws,
+                      const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
                       int dtype, sodt_stream_t st);
-long sodt_frontend_bwd_workspace_bytes(int B, int S);
+long sodt_frontend_bwd_workspace_bytes(int B, int H, int W);
 int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
                       const float* gamma, const float* beta, const void* dout,
-                      float* dw, float* db, float* dgamma, float* dbeta, int B, int S, int ca_ws,
+                      float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
                       float* ws, long ws_bytes, int dtype, sodt_stream_t st);
-/* The same on an H x W image: rgb (B,3,H,W), token grid th x tw = H/4 x W/4, output row (b * th + y) * tw + x.  H % 4 or W % 4
- * non-zero is refused (SODT_EINVAL, nothing launched): the patches are 4 x 4 and are read as 16-byte rows.  The square entries
- * above are the H == W == S call of these. */
-int sodt_frontend_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                         const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
-                         int dtype, sodt_stream_t st);
-long sodt_frontend_bwd_hw_workspace_bytes(int B, int H, int W);
-int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                         const float* gamma, const float* beta, const void* dout,
-                         float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
-                         float* ws, long ws_bytes, int dtype, sodt_stream_t st);
 
 /* General cross-channel attention (window ca_ws in 1..8, optional cyclic shift; backbone_vit.py:469-561, :589-616) as
- * separate stages: e = 4x Conv2d(1->48,k4,s4) embeddings, f32 [B*t*t][192] (caller's workspace); then per pair
- * softmax((q k^T + mask)/2) v + residual + LayerNorm(48).  The backward accumulates d e with atomics (zero it first);
- * dw/db/dgamma/dbeta accumulate.  ca_ws == 1 callers should use the fused sodt_frontend_* instead. */
+ * separate stages: e = 4x Conv2d(1->48,k4,s4) embeddings, f32 [B*th*tw][192] (caller's workspace); then per pair
+ * softmax((q k^T + mask)/2) v + residual + LayerNorm(48).  The roll and the 0 / -100 mask run per axis on the th x tw grid;
+ * refused unless H % 4 == W % 4 == 0 and both th and tw are multiples of ws.  The backward accumulates d e with atomics
+ * (zero it first); dw/db/dgamma/dbeta accumulate.  ca_ws == 1 callers should use the fused sodt_frontend_* instead. */
 int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                          float* e, int B, int S, sodt_stream_t st);
+                          float* e, int B, int H, int W, sodt_stream_t st);
 int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
-                          int B, int S, sodt_stream_t st);
-int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int S, int ws,
+                          int B, int H, int W, sodt_stream_t st);
+int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W, int ws,
                            int shift, int dtype, sodt_stream_t st);
 int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
-                           float* dbeta, int B, int S, int ws, int shift, int dtype, sodt_stream_t st);
-/* The same on an H x W image (th x tw tokens): the roll and the 0 / -100 mask run per axis on the th x tw grid; refused unless
- * H % 4 == W % 4 == 0 and both th and tw are multiples of ws. */
-int sodt_patch_embed4_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                             float* e, int B, int H, int W, sodt_stream_t st);
-int sodt_patch_embed4_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
-                             int B, int H, int W, sodt_stream_t st);
-int sodt_cross_attn_ln_fwd_hw(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W, int ws,
-                              int shift, int dtype, sodt_stream_t st);
-int sodt_cross_attn_ln_bwd_hw(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
-                              float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st);
+                           float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st);
 
 /* BatchNorm2d (eps 1e-3, momentum 0.03) + SiLU of the head's Conv (common.py:38-50,
  * torch_utils.py:150-152), token-major.  stats f64 [SODT_STATS_REPL][2][C] from SODT_EPI_STATS.

@@ -121,14 +121,15 @@ class PrepDesc(C.Structure):
                 ("dst_ld", C.c_int), ("inner_ld", C.c_int)]
 
 
-# name -> argtypes (all return int except sodt_version)
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 class Conv3Geo(C.Structure):
     """sodt_conv3_geo (include/sodt_hip.h): weight-row / input-pixel / output-pixel maps of the direct 3x3 kernels."""
     _fields_ = [("w_row_stride", C.c_int), ("w_row_off", C.c_int), ("in_mul", C.c_int), ("in_i", C.c_int), ("in_j", C.c_int),
                 ("out_mul", C.c_int), ("out_i", C.c_int), ("out_j", C.c_int)]
 
 
+# name -> argtypes of EVERY exported symbol, type for type what include/sodt_hip.h declares (tests/test_abi_and_host.py parses the
+# header and compares); they return int except the ones in RESTYPES
+_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_long, C.c_float
 SIGNATURES = {
     "sodt_nms_candidates": [_P, _I, _I, C.c_float, _I, _P, _P, _I, _P, _P],
     "sodt_nms_workspace_bytes": [_L, C.POINTER(C.c_size_t)],
@@ -153,24 +154,20 @@ SIGNATURES = {
     "sodt_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sodt_window_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_window_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_wmsa_pack_bytes": [_I, _I, _I, _I],
     "sodt_wmsa_pack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sodt_wmsa_block_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_window_attn_sp_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_window_attn_sp_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_window_attn_bwd_wm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_wmsa_block_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "sodt_frontend_fwd": [_P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "sodt_frontend_bwd": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _I, _P],
-    "sodt_patch_embed4_fwd": [_P, _P, _L, _P, _P, _P, _I, _I, _P],
-    "sodt_patch_embed4_bwd": [_P, _P, _L, _P, _P, _P, _I, _I, _P],
-    "sodt_cross_attn_ln_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "sodt_cross_attn_ln_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "sodt_frontend_fwd_hw": [_P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "sodt_frontend_bwd_hw": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _I, _P],
-    "sodt_patch_embed4_fwd_hw": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
-    "sodt_patch_embed4_bwd_hw": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
-    "sodt_cross_attn_ln_fwd_hw": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "sodt_cross_attn_ln_bwd_hw": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_frontend_fwd": [_P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sodt_frontend_bwd_workspace_bytes": [_I, _I, _I],
+    "sodt_frontend_bwd": [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _I, _P],
+    "sodt_patch_embed4_fwd": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
+    "sodt_patch_embed4_bwd": [_P, _P, _L, _P, _P, _P, _I, _I, _I, _P],
+    "sodt_cross_attn_ln_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sodt_cross_attn_ln_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bn_finalize": [_P, _P, _P, _P, _L, _I, _F, _F, _P],
     "sodt_bn_affine": [_P, _P, _P, _P, _P, _I, _P],
     "sodt_bn_silu_fwd": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
@@ -213,11 +210,11 @@ SIGNATURES = {
     "sodt_sr_l1_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P],
     "sodt_sr_l1_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "sodt_anchor_stats_workspace_bytes": [_L, _I, C.POINTER(C.c_size_t)],
-    "sodt_anchor_stats": [_P, _L, _P, _I, _I, _F, _P, C.c_size_t, _P],
+    "sodt_anchor_stats": [_P, _L, _P, _I, _I, _F, _P, C.c_size_t, _P, _P],
     "sodt_anchor_evolve_workspace_bytes": [_L, C.POINTER(C.c_size_t)],
-    "sodt_anchor_evolve": [_P, _L, _F, _P, _I, _P, _P, _I, _P, _P, C.c_size_t],
+    "sodt_anchor_evolve": [_P, _L, _F, _P, _I, _P, _P, _I, _P, _P, C.c_size_t, _P],
     "sodt_kmeans_lloyd_workspace_bytes": [_L, _I, _I, C.POINTER(C.c_size_t)],
-    "sodt_kmeans_lloyd": [_P, _L, _P, _P, _P, _P, _I, _I, C.c_double, _I, _P, C.c_size_t],
+    "sodt_kmeans_lloyd": [_P, _L, _P, _P, _P, _P, _I, _I, C.c_double, _I, _P, C.c_size_t, _P],
     "sodt_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_pixel_shuffle2": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -233,10 +230,20 @@ SIGNATURES = {
     "sodt_conv3x3_c64n8_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_conv3x3_c64n8_dgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_conv3x3_c64n8_wgrad": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "sodt_conv3x3_c64n8_wgrad_scratch_bytes": [],
     "sodt_conv3x3_c64_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
     "sodt_conv3x3_c64_wgrad": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P],
+    "sodt_conv3x3_c64_wgrad_scratch_bytes": [],
     "sodt_debug_wmsa_stamps": [_P, _I],
     "sodt_debug_wmsa_hg_stamps": [_P, _I],
+    "sodt_version": [],
+}
+RESTYPES = {
+    "sodt_version": C.c_char_p,
+    "sodt_wmsa_pack_bytes": _L,
+    "sodt_frontend_bwd_workspace_bytes": _L,
+    "sodt_conv3x3_c64n8_wgrad_scratch_bytes": _L,
+    "sodt_conv3x3_c64_wgrad_scratch_bytes": _L,
 }
 
 _lib = None
@@ -255,24 +262,10 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
-        fn.restype = C.c_int
-    lib.sodt_wmsa_pack_bytes.argtypes = [_I, _I, _I, _I]
-    lib.sodt_wmsa_pack_bytes.restype = C.c_long
-    lib.sodt_frontend_bwd_workspace_bytes.argtypes = [_I, _I]
-    lib.sodt_frontend_bwd_workspace_bytes.restype = C.c_long
-    lib.sodt_frontend_bwd_hw_workspace_bytes.argtypes = [_I, _I, _I]
-    lib.sodt_frontend_bwd_hw_workspace_bytes.restype = C.c_long
-    lib.sodt_conv3x3_c64n8_wgrad_scratch_bytes.argtypes = []
-    lib.sodt_conv3x3_c64n8_wgrad_scratch_bytes.restype = C.c_long
-    lib.sodt_conv3x3_c64_wgrad_scratch_bytes.argtypes = []
-    lib.sodt_conv3x3_c64_wgrad_scratch_bytes.restype = C.c_long
-    lib.sodt_version.restype = C.c_char_p
-    lib.sodt_version.argtypes = []
+        fn.restype = RESTYPES.get(name, C.c_int)
     _lib = lib
     return lib
 
 
 def exported_symbols():
-    return list(SIGNATURES.keys()) + ["sodt_version", "sodt_wmsa_pack_bytes", "sodt_frontend_bwd_workspace_bytes",
-                                           "sodt_frontend_bwd_hw_workspace_bytes",
-                                           "sodt_conv3x3_c64n8_wgrad_scratch_bytes", "sodt_conv3x3_c64_wgrad_scratch_bytes"]
+    return list(SIGNATURES)

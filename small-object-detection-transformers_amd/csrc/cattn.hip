@@ -269,21 +269,16 @@ bool ca_geo(CaGeo& g, int B, int H, int W, int ws, int shift, long ir_bstride) {
 
 }  // namespace
 
-extern "C" int sodt_patch_embed4_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                        float* e, int B, int H, int W, sodt_stream_t st) {
+extern "C" int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                     float* e, int B, int H, int W, sodt_stream_t st) {
   CaGeo g;
   if (!rgb || !ir || !w || !b || !e || !ca_geo(g, B, H, W, 1, 0, ir_bstride)) return SODT_EINVAL;
   const long ntok = (long)B * g.th * g.tw;
   return sodt_launch<patch_embed4_fwd_kernel>(dim3((unsigned)((ntok * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)st, rgb, ir, w, b, e, g, ntok);
 }
 
-extern "C" int sodt_patch_embed4_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                     float* e, int B, int S, sodt_stream_t st) {
-  return sodt_patch_embed4_fwd_hw(rgb, ir, ir_bstride, w, b, e, B, S, S, st);
-}
-
-extern "C" int sodt_patch_embed4_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
-                                        int B, int H, int W, sodt_stream_t st) {
+extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
+                                     int B, int H, int W, sodt_stream_t st) {
   CaGeo g;
   if (!rgb || !ir || !de || !dw || !db || !ca_geo(g, B, H, W, 1, 0, ir_bstride)) return SODT_EINVAL;
   const long ntok = (long)B * g.th * g.tw;
@@ -291,13 +286,8 @@ extern "C" int sodt_patch_embed4_bwd_hw(const float* rgb, const float* ir, long 
   return sodt_launch<patch_embed4_bwd_kernel>(dim3((4 * CE * 17 + 255) / 256, gy), dim3(256), 0, (hipStream_t)st, rgb, ir, de, dw, db, g, ntok);
 }
 
-extern "C" int sodt_patch_embed4_bwd(const float* rgb, const float* ir, long ir_bstride, const float* de, float* dw, float* db,
-                                     int B, int S, sodt_stream_t st) {
-  return sodt_patch_embed4_bwd_hw(rgb, ir, ir_bstride, de, dw, db, B, S, S, st);
-}
-
-extern "C" int sodt_cross_attn_ln_fwd_hw(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W,
-                                         int ws, int shift, int dtype, sodt_stream_t st) {
+extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int H, int W,
+                                      int ws, int shift, int dtype, sodt_stream_t st) {
   CaGeo g;
   if (!e || !gamma || !beta || !out || !ca_geo(g, B, H, W, ws, shift, 0)) return SODT_EINVAL;
   const long ntok = (long)B * g.th * g.tw;
@@ -307,13 +297,8 @@ extern "C" int sodt_cross_attn_ln_fwd_hw(const float* e, const float* gamma, con
   return SODT_EINVAL;
 }
 
-extern "C" int sodt_cross_attn_ln_fwd(const float* e, const float* gamma, const float* beta, void* out, int B, int S, int ws,
-                                      int shift, int dtype, sodt_stream_t st) {
-  return sodt_cross_attn_ln_fwd_hw(e, gamma, beta, out, B, S, S, ws, shift, dtype, st);
-}
-
-extern "C" int sodt_cross_attn_ln_bwd_hw(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
-                                         float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st) {
+extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
+                                      float* dbeta, int B, int H, int W, int ws, int shift, int dtype, sodt_stream_t st) {
   CaGeo g;
   if (!e || !gamma || !dout || !de || !dgamma || !dbeta || !ca_geo(g, B, H, W, ws, shift, 0)) return SODT_EINVAL;
   const long ntok = (long)B * g.th * g.tw;
@@ -321,9 +306,4 @@ extern "C" int sodt_cross_attn_ln_bwd_hw(const float* e, const float* gamma, con
   if (dtype == SODT_BF16) return sodt_launch<cross_attn_ln_bwd_kernel<bf16>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const bf16*)dout, de, dgamma, dbeta, g, ntok);
   if (dtype == SODT_F32) return sodt_launch<cross_attn_ln_bwd_kernel<float>>(dim3(gr), dim3(128), 0, (hipStream_t)st, e, gamma, (const float*)dout, de, dgamma, dbeta, g, ntok);
   return SODT_EINVAL;
-}
-
-extern "C" int sodt_cross_attn_ln_bwd(const float* e, const float* gamma, const void* dout, float* de, float* dgamma,
-                                      float* dbeta, int B, int S, int ws, int shift, int dtype, sodt_stream_t st) {
-  return sodt_cross_attn_ln_bwd_hw(e, gamma, dout, de, dgamma, dbeta, B, S, S, ws, shift, dtype, st);
 }

@@ -374,9 +374,9 @@ bool fe_geo(FeGeo& g, int B, int H, int W, long ir_bstride) {
 
 }  // namespace
 
-extern "C" int sodt_frontend_fwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                    const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
-                                    int dtype, sodt_stream_t st) {
+extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                 const float* gamma, const float* beta, void* out, int B, int H, int W, int ca_ws,
+                                 int dtype, sodt_stream_t st) {
   FeGeo g;
   if (!rgb || !ir || !w || !b || !gamma || !beta || !out || !fe_geo(g, B, H, W, ir_bstride)) return SODT_EINVAL;
   if (ca_ws != 1) return SODT_EINVAL;   // general window path: sodt_cross_channel_attn_* (cattn.hip)
@@ -389,23 +389,15 @@ extern "C" int sodt_frontend_fwd_hw(const float* rgb, const float* ir, long ir_b
   return SODT_EINVAL;
 }
 
-extern "C" int sodt_frontend_fwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                 const float* gamma, const float* beta, void* out, int B, int S, int ca_ws,
-                                 int dtype, sodt_stream_t st) {
-  return sodt_frontend_fwd_hw(rgb, ir, ir_bstride, w, b, gamma, beta, out, B, S, S, ca_ws, dtype, st);
-}
-
-extern "C" long sodt_frontend_bwd_hw_workspace_bytes(int B, int H, int W) {
+extern "C" long sodt_frontend_bwd_workspace_bytes(int B, int H, int W) {
   (void)B; (void)H; (void)W;
   return (long)FE_BWD_GRID * FE_PART * (long)sizeof(float);
 }
 
-extern "C" long sodt_frontend_bwd_workspace_bytes(int B, int S) { return sodt_frontend_bwd_hw_workspace_bytes(B, S, S); }
-
-extern "C" int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                    const float* gamma, const float* beta, const void* dout,
-                                    float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
-                                    float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
+extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
+                                 const float* gamma, const float* beta, const void* dout,
+                                 float* dw, float* db, float* dgamma, float* dbeta, int B, int H, int W, int ca_ws,
+                                 float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
   (void)beta;
   FeGeo g;
   if (!rgb || !ir || !w || !b || !gamma || !dout || !dw || !db || !dgamma || !dbeta || !fe_geo(g, B, H, W, ir_bstride)) return SODT_EINVAL;
@@ -415,7 +407,7 @@ extern "C" int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_b
   const int nblk = (int)((ntok + 63) / 64);
   // the two-stage reduction pays once there are enough workgroups for the direct atomics to queue up; without a
   // workspace fewer, longer-lived workgroups keep the final burst of atomics short
-  const bool two_stage = ws && ws_bytes >= sodt_frontend_bwd_hw_workspace_bytes(B, H, W) && nblk > 64;
+  const bool two_stage = ws && ws_bytes >= sodt_frontend_bwd_workspace_bytes(B, H, W) && nblk > 64;
   const int cap = two_stage ? FE_BWD_GRID : FE_BWD_GRID / 2;
   const unsigned blocks = (unsigned)(nblk < cap ? nblk : cap);
   hipStream_t s = (hipStream_t)st;
@@ -427,11 +419,4 @@ extern "C" int sodt_frontend_bwd_hw(const float* rgb, const float* ir, long ir_b
   if (rc || !two_stage) return rc;
   return sodt_launch<frontend_bwd_reduce_kernel>(dim3(FE_PART / 64, (blocks + FE_RG - 1) / FE_RG), dim3(64), 0, s, ws, (int)blocks,
                                                  dw, db, dgamma, dbeta);
-}
-
-extern "C" int sodt_frontend_bwd(const float* rgb, const float* ir, long ir_bstride, const float* w, const float* b,
-                                 const float* gamma, const float* beta, const void* dout,
-                                 float* dw, float* db, float* dgamma, float* dbeta, int B, int S, int ca_ws,
-                                 float* ws, long ws_bytes, int dtype, sodt_stream_t st) {
-  return sodt_frontend_bwd_hw(rgb, ir, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, S, S, ca_ws, ws, ws_bytes, dtype, st);
 }

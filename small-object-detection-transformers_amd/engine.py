@@ -634,20 +634,12 @@ class Engine:
         cb = self.model.image_encoder.chan_block
         ca_ws, ca_shift = int(cb.window_size), int(cb.shift_size)
         irs = x_ir.shape[1] * H * W
-        # a square input keeps the square entry points (and their names in every recorded list); H != W takes the _hw ones
         if ca_ws == 1:      # the shipped configuration (backbone_vit.py:438): fused kernel
-            if H == W:
-                ops.frontend_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, H, 1)
-            else:
-                ops.frontend_fwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, H, W, 1)
+            ops.frontend_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], x0, B, H, W)
         else:               # general window / shift form of CAttentionBlock
             e = plan.buf("fe.e", (T1, 192), torch.float32)
-            if H == W:
-                ops.patch_embed4_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], e, B, H)
-                ops.cross_attn_ln_fwd(e, fe["g"], fe["be"], x0, B, H, ca_ws, ca_shift)
-            else:
-                ops.patch_embed4_fwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], e, B, H, W)
-                ops.cross_attn_ln_fwd_hw(e, fe["g"], fe["be"], x0, B, H, W, ca_ws, ca_shift)
+            ops.patch_embed4_fwd(x_rgb, x_ir, irs, fe["w"], fe["b"], e, B, H, W)
+            ops.cross_attn_ln_fwd(e, fe["g"], fe["be"], x0, B, H, W, ca_ws, ca_shift)
         # (3) encoder + head (recorded)
         if plan.fwd_main is None:
             with ops.Recorder() as rec:
@@ -1425,21 +1417,13 @@ class Engine:
         irs = x_ir.shape[1] * H * W
         gw, gb, gg, gbe, dx0 = self.g_fe_w, self.g_fe_b, self.g_fe_g, self.g_fe_be, plan.bufs["g.dx0"]
         if ca_ws == 1:
-            if H == W:
-                ws = plan.buf("fe.ws", (ops.frontend_bwd_workspace_bytes(B, H) // 4,), torch.float32)
-                ops.frontend_bwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], dx0, gw, gb, gg, gbe, B, H, 1, ws)
-            else:
-                ws = plan.buf("fe.ws", (ops.frontend_bwd_hw_workspace_bytes(B, H, W) // 4,), torch.float32)
-                ops.frontend_bwd_hw(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], dx0, gw, gb, gg, gbe, B, H, W, 1, ws)
+            ws = plan.buf("fe.ws", (ops.frontend_bwd_workspace_bytes(B, H, W) // 4,), torch.float32)
+            ops.frontend_bwd(x_rgb, x_ir, irs, fe["w"], fe["b"], fe["g"], fe["be"], dx0, gw, gb, gg, gbe, B, H, W, ws=ws)
         else:
             de = plan.buf("fe.de", (B * (H // 4) * (W // 4), 192), torch.float32)
             ops.zero_(de)
-            if H == W:
-                ops.cross_attn_ln_bwd(plan.bufs["fe.e"], fe["g"], dx0, de, gg, gbe, B, H, ca_ws, ca_shift)
-                ops.patch_embed4_bwd(x_rgb, x_ir, irs, de, gw, gb, B, H)
-            else:
-                ops.cross_attn_ln_bwd_hw(plan.bufs["fe.e"], fe["g"], dx0, de, gg, gbe, B, H, W, ca_ws, ca_shift)
-                ops.patch_embed4_bwd_hw(x_rgb, x_ir, irs, de, gw, gb, B, H, W)
+            ops.cross_attn_ln_bwd(plan.bufs["fe.e"], fe["g"], dx0, de, gg, gbe, B, H, W, ca_ws, ca_shift)
+            ops.patch_embed4_bwd(x_rgb, x_ir, irs, de, gw, gb, B, H, W)
 
     def _zero_frozen(self, plan: Plan, lo, hi):
         """Frozen parameters' slices in [lo, hi) of the flat buffer that a launch fusing dX with parameter gradients may have

@@ -49,16 +49,14 @@ class _LossFn(torch.autograd.Function):
         nt = int(targets.shape[0])
         dpred = torch.empty_like(pred)
         out = torch.empty(4, device=pred.device, dtype=torch.float32)
-        nbytes = C.c_size_t(0)
-        lib = L.load()
-        if lib.sodt_yolo_loss_workspace_bytes(B * na * ny * nx, nt, nc, C.byref(nbytes)) != 0:
-            raise RuntimeError("sodt_yolo_loss_workspace_bytes: unsupported shape (nc <= 32)")
-        ws = torch.empty(nbytes.value, device=pred.device, dtype=torch.uint8)
+        nbytes = ops._ws_bytes("sodt_yolo_loss_workspace_bytes", B * na * ny * nx, nt, nc,
+                               msg="sodt_yolo_loss_workspace_bytes: unsupported shape (nc <= 32)")
+        ws = torch.empty(nbytes, device=pred.device, dtype=torch.uint8)
         focal = hyp["fl_gamma"] > 0
         ops._launch("sodt_yolo_loss_fl" if focal else "sodt_yolo_loss", pred.data_ptr(), targets.data_ptr() if nt else None, nt,
                     anchors.data_ptr(), B, na, ny, nx, nc, C.c_float(hyp["box"]), C.c_float(hyp["cls"]), C.c_float(hyp["cls_pw"]),
                     C.c_float(hyp["obj"]), C.c_float(hyp["obj_pw"]), C.c_float(hyp["anchor_t"]), C.c_float(gr),
-                    *((C.c_float(hyp["fl_gamma"]),) if focal else ()), ws.data_ptr(), nbytes.value, dpred.data_ptr(), out.data_ptr())
+                    *((C.c_float(hyp["fl_gamma"]),) if focal else ()), ws.data_ptr(), nbytes, dpred.data_ptr(), out.data_ptr())
         ctx.save_for_backward(dpred)
         # independent tensors, not slices of `out`: views of one buffer returned by a multi-output Function are
         # MULTI_OUTPUT_NODE views on which the reference loop's in-place `loss *= opt.world_size` (Train.py:440),

@@ -86,6 +86,15 @@ def _launch(name: str, *args) -> None:
         _active_recorder.append((fn, args, name, _tag))
 
 
+def _ws_bytes(name: str, *args, hint: str = "see include/sodt_hip.h", msg: Optional[str] = None) -> int:
+    """A ``sodt_*_workspace_bytes(..., size_t* bytes)`` query; a refusal raises ``msg``, or the status with ``hint``."""
+    b = C.c_size_t(0)
+    rc = getattr(_lib, name)(*args, C.byref(b))
+    if rc != 0:
+        raise RuntimeError(msg or f"{name} failed with status {rc}" + (f" ({hint})" if hint else ""))
+    return int(b.value)
+
+
 def dt_code(t: torch.Tensor) -> int:
     if t.dtype == torch.bfloat16:
         return L.BF16
@@ -469,69 +478,37 @@ def rows_from_nchw_f32(y, rows, B, Cc, H, W):
     _launch("sodt_rows_from_nchw_f32", y.data_ptr(), rows.data_ptr(), rows.shape[-1], B, Cc, H, W, dt_code(rows))
 
 
-def frontend_fwd(rgb, ir_plane, ir_bstride, w, b, gamma, beta, out, B, S, ca_ws=1):
+def frontend_fwd(rgb, ir_plane, ir_bstride, w, b, gamma, beta, out, B, H, W, *, ca_ws=1):
+    """The front end on an H x W image: out is [B * (H/4) * (W/4)][192], row (b * H/4 + y) * W/4 + x."""
     _launch("sodt_frontend_fwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(out),
-            B, S, ca_ws, dt_code(out))
-
-
-def frontend_bwd_workspace_bytes(B: int, S: int) -> int:
-    return int(_lib.sodt_frontend_bwd_workspace_bytes(B, S))
-
-
-def frontend_bwd(rgb, ir_plane, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, S, ca_ws=1, ws=None):
-    """``ws``: f32 scratch of ``frontend_bwd_workspace_bytes`` (two-stage reduction); None = direct atomics."""
-    _launch("sodt_frontend_bwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(dout),
-            _p(dw), _p(db), _p(dgamma), _p(dbeta), B, S, ca_ws, _p(ws), 0 if ws is None else ws.numel() * ws.element_size(),
-            dt_code(dout))
-
-
-def frontend_fwd_hw(rgb, ir_plane, ir_bstride, w, b, gamma, beta, out, B, H, W, ca_ws=1):
-    """sodt_frontend_fwd on an H x W image: out is [B * (H/4) * (W/4)][192], row (b * H/4 + y) * W/4 + x."""
-    _launch("sodt_frontend_fwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(out),
             B, H, W, ca_ws, dt_code(out))
 
 
-def frontend_bwd_hw_workspace_bytes(B: int, H: int, W: int) -> int:
-    return int(_lib.sodt_frontend_bwd_hw_workspace_bytes(B, H, W))
+def frontend_bwd_workspace_bytes(B: int, H: int, W: int) -> int:
+    return int(_lib.sodt_frontend_bwd_workspace_bytes(B, H, W))
 
 
-def frontend_bwd_hw(rgb, ir_plane, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, H, W, ca_ws=1, ws=None):
-    """``ws``: f32 scratch of ``frontend_bwd_hw_workspace_bytes`` (two-stage reduction); None = direct atomics."""
-    _launch("sodt_frontend_bwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(dout),
+def frontend_bwd(rgb, ir_plane, ir_bstride, w, b, gamma, beta, dout, dw, db, dgamma, dbeta, B, H, W, *, ca_ws=1, ws=None):
+    """``ws``: f32 scratch of ``frontend_bwd_workspace_bytes`` (two-stage reduction); None = direct atomics."""
+    _launch("sodt_frontend_bwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(gamma), _p(beta), _p(dout),
             _p(dw), _p(db), _p(dgamma), _p(dbeta), B, H, W, ca_ws, _p(ws), 0 if ws is None else ws.numel() * ws.element_size(),
             dt_code(dout))
 
 
-def patch_embed4_fwd(rgb, ir_plane, ir_bstride, w, b, e, B, S):
-    _launch("sodt_patch_embed4_fwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(e), B, S)
+def patch_embed4_fwd(rgb, ir_plane, ir_bstride, w, b, e, B, H, W):
+    _launch("sodt_patch_embed4_fwd", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(e), B, H, W)
 
 
-def patch_embed4_bwd(rgb, ir_plane, ir_bstride, de, dw, db, B, S):
-    _launch("sodt_patch_embed4_bwd", _p(rgb), _p(ir_plane), ir_bstride, _p(de), _p(dw), _p(db), B, S)
+def patch_embed4_bwd(rgb, ir_plane, ir_bstride, de, dw, db, B, H, W):
+    _launch("sodt_patch_embed4_bwd", _p(rgb), _p(ir_plane), ir_bstride, _p(de), _p(dw), _p(db), B, H, W)
 
 
-def cross_attn_ln_fwd(e, gamma, beta, out, B, S, ws, shift):
-    _launch("sodt_cross_attn_ln_fwd", _p(e), _p(gamma), _p(beta), _p(out), B, S, ws, shift, dt_code(out))
+def cross_attn_ln_fwd(e, gamma, beta, out, B, H, W, ws, shift):
+    _launch("sodt_cross_attn_ln_fwd", _p(e), _p(gamma), _p(beta), _p(out), B, H, W, ws, shift, dt_code(out))
 
 
-def cross_attn_ln_bwd(e, gamma, dout, de, dgamma, dbeta, B, S, ws, shift):
-    _launch("sodt_cross_attn_ln_bwd", _p(e), _p(gamma), _p(dout), _p(de), _p(dgamma), _p(dbeta), B, S, ws, shift, dt_code(dout))
-
-
-def patch_embed4_fwd_hw(rgb, ir_plane, ir_bstride, w, b, e, B, H, W):
-    _launch("sodt_patch_embed4_fwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(w), _p(b), _p(e), B, H, W)
-
-
-def patch_embed4_bwd_hw(rgb, ir_plane, ir_bstride, de, dw, db, B, H, W):
-    _launch("sodt_patch_embed4_bwd_hw", _p(rgb), _p(ir_plane), ir_bstride, _p(de), _p(dw), _p(db), B, H, W)
-
-
-def cross_attn_ln_fwd_hw(e, gamma, beta, out, B, H, W, ws, shift):
-    _launch("sodt_cross_attn_ln_fwd_hw", _p(e), _p(gamma), _p(beta), _p(out), B, H, W, ws, shift, dt_code(out))
-
-
-def cross_attn_ln_bwd_hw(e, gamma, dout, de, dgamma, dbeta, B, H, W, ws, shift):
-    _launch("sodt_cross_attn_ln_bwd_hw", _p(e), _p(gamma), _p(dout), _p(de), _p(dgamma), _p(dbeta), B, H, W, ws, shift, dt_code(dout))
+def cross_attn_ln_bwd(e, gamma, dout, de, dgamma, dbeta, B, H, W, ws, shift):
+    _launch("sodt_cross_attn_ln_bwd", _p(e), _p(gamma), _p(dout), _p(de), _p(dgamma), _p(dbeta), B, H, W, ws, shift, dt_code(dout))
 
 
 def bn_finalize(stats, mean_rstd, running_mean, running_var, count, Cc, eps, momentum):
@@ -677,11 +654,7 @@ def nms_candidates(z_img, conf_thres, multi_label, class_allow, keys, count):
 
 
 def nms_workspace_bytes(n_total: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_nms_workspace_bytes(int(n_total), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_nms_workspace_bytes failed with status {rc}")
-    return int(b.value)
+    return _ws_bytes("sodt_nms_workspace_bytes", int(n_total), hint="")
 
 
 def nms_select(z_img, keys, n_total, iou_thres, agnostic, ws, out, out_index, out_count):
@@ -692,11 +665,8 @@ def nms_select(z_img, keys, n_total, iou_thres, agnostic, ws, out, out_index, ou
 
 def nms_batch_workspace_bytes(B: int, rows: int, nc: int, multi_label) -> int:
     """Scratch bytes of nms_batch (general.py:425-512 for a batch): a function of B, rows = N + lab_cap, nc, multi_label."""
-    b = C.c_size_t(0)
-    rc = _lib.sodt_nms_batch_workspace_bytes(int(B), int(rows), int(nc), int(bool(multi_label)), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_nms_batch_workspace_bytes failed with status {rc} (B <= 4096, B * rows * nc < 2^31)")
-    return int(b.value)
+    return _ws_bytes("sodt_nms_batch_workspace_bytes", int(B), int(rows), int(nc), int(bool(multi_label)),
+                     hint="B <= 4096, B * rows * nc < 2^31")
 
 
 def nms_batch(z, labels, nlab, conf_thres, iou_thres, multi_label, class_allow, agnostic, ws, out_rows, out_index, out_off):
@@ -718,11 +688,7 @@ def wbf_candidates(z, conf_thres, image_size, boxes, scores, labels, src, counts
 
 
 def wbf_fuse_workspace_bytes(B: int, cap: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_wbf_fuse_workspace_bytes(int(B), int(cap), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_wbf_fuse_workspace_bytes failed with status {rc} (B <= 65535, B * cap <= 2^30)")
-    return int(b.value)
+    return _ws_bytes("sodt_wbf_fuse_workspace_bytes", int(B), int(cap), hint="B <= 65535, B * cap <= 2^30")
 
 
 def wbf_fuse(boxes, scores, labels, model, src, counts, weights, iou_thr, skip_box_thr, conf_type, allows_overflow, ws,
@@ -737,11 +703,7 @@ def wbf_fuse(boxes, scores, labels, model, src, counts, weights, iou_thr, skip_b
 
 
 def eval_match_workspace_bytes(B: int, n_det: int, nt: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_eval_match_workspace_bytes(int(B), int(n_det), int(nt), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_eval_match_workspace_bytes failed with status {rc}")
-    return int(b.value)
+    return _ws_bytes("sodt_eval_match_workspace_bytes", int(B), int(n_det), int(nt), hint="")
 
 
 def eval_match(det, det_off, targets, geom, iouv, ws, correct, tcls_out):
@@ -754,11 +716,7 @@ def eval_match(det, det_off, targets, geom, iouv, ws, correct, tcls_out):
 
 
 def ap_per_class_workspace_bytes(n: int, nt: int, nc: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_ap_per_class_workspace_bytes(int(n), int(nt), int(nc), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_ap_per_class_workspace_bytes failed with status {rc} (nc must be in [1, 4096])")
-    return int(b.value)
+    return _ws_bytes("sodt_ap_per_class_workspace_bytes", int(n), int(nt), int(nc), hint="nc must be in [1, 4096]")
 
 
 def ap_per_class(tp, conf, pred_cls, target_cls, nc, ws, p, r, f1, ap, classes, nt_count, info):
@@ -768,11 +726,7 @@ def ap_per_class(tp, conf, pred_cls, target_cls, nc, ws, p, r, f1, ap, classes, 
 
 
 def confusion_workspace_bytes(B: int, n_det: int, nt: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_confusion_update_workspace_bytes(int(B), int(n_det), int(nt), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_confusion_update_workspace_bytes failed with status {rc}")
-    return int(b.value)
+    return _ws_bytes("sodt_confusion_update_workspace_bytes", int(B), int(n_det), int(nt), hint="")
 
 
 def confusion_update(det, det_off, targets, geom, nc, conf, iou_thres, ws, matrix, info):
@@ -899,11 +853,7 @@ def adam_ema_step_ctl(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr
 
 
 def sr_l1_workspace_bytes(B: int, C_: int, H: int, W: int) -> int:
-    b = C.c_size_t(0)
-    rc = _lib.sodt_sr_l1_workspace_bytes(int(B), int(C_), int(H), int(W), C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"sodt_sr_l1_workspace_bytes failed with status {rc} (B * C <= 65535, H * W < 2^31)")
-    return int(b.value)
+    return _ws_bytes("sodt_sr_l1_workspace_bytes", int(B), int(C_), int(H), int(W), hint="B * C <= 65535, H * W < 2^31")
 
 
 def _sr_l1_args(sr, rgb, ir, mode):
@@ -923,14 +873,6 @@ def sr_l1_fwd(sr, rgb, ir, mode, ws, loss):
 def sr_l1_bwd(sr, rgb, ir, mode, upstream, dsr):
     """dsr = upstream * w / n_group * sign(sr - target) in one pass; upstream is a one-element f32 DEVICE tensor."""
     _launch("sodt_sr_l1_bwd", *_sr_l1_args(sr, rgb, ir, mode), _p(upstream), _p(dsr))
-
-
-def _ws_bytes(name: str, *args) -> int:
-    b = C.c_size_t(0)
-    rc = getattr(_lib, name)(*args, C.byref(b))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with status {rc} (see include/sodt_hip.h)")
-    return int(b.value)
 
 
 def anchor_stats_workspace_bytes(N: int, S: int) -> int:

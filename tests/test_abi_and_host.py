@@ -25,9 +25,158 @@ def test_library_exports_every_declared_symbol(pkg):
     assert len(declared) >= 24
     for name in declared:
         assert hasattr(lib, name), f"{name} is declared in include/sodt_hip.h but not exported by libsodt_hip.so"
-    bound = set(L.exported_symbols())
-    assert set(declared) == bound, (sorted(set(declared) - bound), sorted(bound - set(declared)))
+    assert set(declared) == set(L.exported_symbols())        # (which side lacks what: test_signatures_equal_the_header_type_for_type)
     assert lib.sodt_version().startswith(b"sodt_hip")
+
+
+HEADER = os.path.join(ROOT, "include", "sodt_hip.h")
+SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+           "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong}
+# the header's ten records and the ctypes classes of _lib.py that mirror them
+STRUCTS = {"sodt_seg": "Seg", "sodt_aspec": "ASpec", "sodt_gemm_args": "GemmArgs", "sodt_gemm_tn_args": "GemmTnArgs",
+           "sodt_linbwd_args": "LinBwdArgs", "sodt_conv3_geo": "Conv3Geo", "sodt_tta_pass": "TtaPass",
+           "sodt_detect_args": "DetectArgs", "sodt_prep_desc": "PrepDesc", "sodt_step_ctl": "StepCtl"}
+
+
+def _header_code():
+    """include/sodt_hip.h without comments and preprocessor lines."""
+    src = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    return re.sub(r"^[ \t]*#[^\n]*$", " ", src, flags=re.M)
+
+
+def _c_type(decl, named):
+    """'const float* rgb' -> ('float', 1): the base type and the pointer depth of a declaration, the name dropped."""
+    tok = [t for t in re.findall(r"\w+|\*", decl) if t != "const"]
+    if named:
+        assert len(tok) >= 2 and re.fullmatch(r"[A-Za-z_]\w*", tok[-1]) and tok[-1] not in ("int", "long", "char", "void"), decl
+        tok = tok[:-1]
+    return " ".join(t for t in tok if t != "*"), tok.count("*")
+
+
+def header_prototypes():
+    """name -> ((return base, depth), [(parameter base, depth), ...]) of every sodt_* prototype of the header."""
+    code = re.sub(r"typedef\s+struct\s*\{[^{}]*\}\s*\w+\s*;", " ", _header_code(), flags=re.S)
+    protos = {}
+    for stmt in code.split(";"):
+        m = re.fullmatch(r"(.*?)\b(sodt_\w+)\s*\((.*)\)", stmt.strip(), flags=re.S)
+        if not m:
+            assert "(" not in stmt, f"a statement of the header with parentheses that is no sodt_* prototype: {stmt.strip()!r}"
+            continue
+        ret, name, params = m.groups()
+        assert name not in protos, f"{name} is declared twice"
+        params = [] if params.strip() == "void" else [_c_type(p, named=True) for p in params.split(",")]
+        protos[name] = (_c_type(ret, named=False), params)
+    return protos
+
+
+def _matches(L, base, depth, ct):
+    """Does the ctypes type ``ct`` bind a C parameter of type ``base`` with ``depth`` stars?"""
+    if depth == 0 and base != "sodt_stream_t":
+        return base in SCALARS and ct is SCALARS[base]
+    if ct is ctypes.c_void_p:
+        return True
+    pointee = {"size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+    pointee.update({c: getattr(L, py) for c, py in STRUCTS.items()})
+    return depth == 1 and base in pointee and ct is ctypes.POINTER(pointee[base])
+
+
+def abi_findings(L):
+    """Every disagreement between the header's prototypes and _lib.SIGNATURES / _lib.RESTYPES, one line each."""
+    protos, out = header_prototypes(), []
+    tn = lambda t: getattr(t, "__name__", repr(t))
+    for name in sorted(set(protos) - set(L.SIGNATURES)):
+        out.append(f"{name}: declared in include/sodt_hip.h, not in SIGNATURES")
+    for name in sorted(set(L.SIGNATURES) - set(protos)):
+        out.append(f"{name}: in SIGNATURES, not declared in include/sodt_hip.h")
+    for name in sorted(set(L.RESTYPES) - set(L.SIGNATURES)):
+        out.append(f"{name}: in RESTYPES, not in SIGNATURES")
+    for name in sorted(set(protos) & set(L.SIGNATURES)):
+        (rbase, rdepth), params = protos[name]
+        bound, res = L.SIGNATURES[name], L.RESTYPES.get(name, ctypes.c_int)
+        want = ctypes.c_char_p if (rbase, rdepth) == ("char", 1) else SCALARS.get(rbase) if rdepth == 0 else None
+        if res is not want:
+            out.append(f"{name}: returns {rbase}{'*' * rdepth} in the header, {tn(res)} in RESTYPES")
+        if len(params) != len(bound):
+            out.append(f"{name}: {len(params)} parameters in the header, {len(bound)} in SIGNATURES")
+            continue
+        for i, ((base, depth), ct) in enumerate(zip(params, bound)):
+            if not _matches(L, base, depth, ct):
+                out.append(f"{name}: argument {i} is {base}{'*' * depth} in the header, {tn(ct)} in SIGNATURES")
+    return out
+
+
+def test_signatures_equal_the_header_type_for_type(pkg):
+    """include/sodt_hip.h is the contract: every prototype is bound in _lib.SIGNATURES (and nothing else is), with the header's
+    return type and each parameter's type - scalars exactly, a pointer or the stream as c_void_p or as a POINTER to the
+    header's pointee - and the loaded library exports every one of them with exactly these types set."""
+    L = pkg._lib
+    protos = header_prototypes()
+    assert len(protos) == len(header_symbols()) >= 24           # the parser sees what the line-anchored pattern sees
+    found = abi_findings(L)
+    assert not found, "\n" + "\n".join(found)
+    lib = L.load()
+    assert L.exported_symbols() == list(L.SIGNATURES)
+    for name, argtypes in L.SIGNATURES.items():
+        fn = getattr(lib, name)                                  # AttributeError: not exported by libsodt_hip.so
+        assert list(fn.argtypes) == list(argtypes) and fn.restype is L.RESTYPES.get(name, ctypes.c_int), name
+
+
+def _layout_program(L):
+    """A host program that prints sizeof of every record of the header and offsetof / sizeof of every field; the field names
+    are those of the ctypes classes, so one the header does not have stops the compile."""
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "sodt_hip.h"',
+             '#define FIELD(T, f) printf(#T "." #f " %zu %zu\\n", offsetof(T, f), sizeof(((T*)0)->f))',
+             "int main(void) {"]
+    for c, py in STRUCTS.items():
+        lines.append(f'  printf("{c} %zu\\n", sizeof({c}));')
+        lines += [f"  FIELD({c}, {f[0]});" for f in getattr(L, py)._fields_]
+    return "\n".join(lines + ["  return 0;", "}", ""])
+
+
+def test_every_ctypes_record_has_the_header_layout(pkg, tmp_path):
+    """All ten records, field by field: the header compiled on the host against ctypes.sizeof / .offset / .size."""
+    import subprocess
+    from test_routes_host import _compiler
+    L = pkg._lib
+    declared = re.findall(r"typedef\s+struct\s*\{[^{}]*\}\s*(\w+)\s*;", _header_code(), flags=re.S)
+    assert sorted(declared) == sorted(STRUCTS) and len(STRUCTS) == 10
+    classes = [v for v in vars(L).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure]
+    assert sorted(c.__name__ for c in classes) == sorted(STRUCTS.values())
+    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
+    src.write_text(_layout_program(L))
+    r = subprocess.run([_compiler(), "-std=c++17", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    got = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in r.stdout.splitlines()}
+    want = {}
+    for c, py in STRUCTS.items():
+        cls = getattr(L, py)
+        want[c] = (ctypes.sizeof(cls),)
+        for f in cls._fields_:
+            want[f"{c}.{f[0]}"] = (getattr(cls, f[0]).offset, getattr(cls, f[0]).size)
+    assert set(got) == set(want)
+    bad = [f"{k}: header {got[k]}, ctypes {want[k]}" for k in want if got[k] != want[k]]
+    assert not bad, "\n" + "\n".join(bad)
+    # a field the header has and the class lacks leaves a gap or a short record: sizes and offsets above cover both, and
+    # the counts close it
+    for c, py in STRUCTS.items():
+        body = re.search(r"typedef\s+struct\s*\{([^{}]*)\}\s*" + c + r"\s*;", _header_code(), flags=re.S).group(1)
+        names = [re.search(r"(\w+)\s*(?:\[[^\]]*\])?\s*$", d).group(1) for s in body.split(";") if s.strip() for d in s.split(",")]
+        assert names == [f[0] for f in getattr(L, py)._fields_], c
+
+
+def test_frontend_wrappers_take_the_window_and_the_workspace_by_keyword_only(ops):
+    """A call written for the former square wrappers, (..., B, S, 1) or (..., B, S, 1, ws), must not run with W = 1."""
+    import inspect
+    for fn, names in ((ops.frontend_fwd, ("ca_ws",)), (ops.frontend_bwd, ("ca_ws", "ws"))):
+        par = inspect.signature(fn).parameters
+        assert list(par)[-len(names) - 3:-len(names)] == ["B", "H", "W"]
+        assert all(par[n].kind is inspect.Parameter.KEYWORD_ONLY for n in names)
+    with pytest.raises(TypeError):
+        ops.frontend_fwd(*[None] * 8, 1, 64, 64, 1)
 
 
 def test_ctypes_record_layout(pkg):

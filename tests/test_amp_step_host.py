@@ -1,5 +1,5 @@
-"""Host-side checks of the optimizers' control path (no GPU): the three C entries are declared in the header, exported by the
-library and bound; the ctypes record matches the layout the header documents; the constructors refuse a max_grad_norm that
+"""Host-side checks of the optimizers' control path (no GPU): the _ctl steps take the plain steps' arguments with one record
+pointer; the ctypes record matches the layout the header documents; the constructors refuse a max_grad_norm that
 is not positive; both optimizers tell torch.amp.GradScaler that they take its scale and found-inf tensors themselves; Adam's
 step count travels in state_dict(); the entries refuse null or misaligned control pointers before anything is launched."""
 import ctypes as C
@@ -13,17 +13,10 @@ import torch
 
 PKG = "small-object-detection-transformers_amd"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("sodt_grad_stats", "sodt_sgd_ema_step_ctl", "sodt_adam_ema_step_ctl")
 
 
 def test_control_entries_declared_exported_and_bound(pkg):
-    L = pkg._lib
-    lib = L.load()
-    hdr = open(os.path.join(ROOT, "include", "sodt_hip.h")).read()
-    for name in NEW:
-        assert re.search(rf"^int\s+{name}\s*\(", hdr, flags=re.M), f"{name} is not declared in include/sodt_hip.h"
-        assert name in L.SIGNATURES and name in L.exported_symbols()
-        assert hasattr(lib, name), f"{name} is not exported by libsodt_hip.so"
+    L = pkg._lib                    # (declared, exported, bound type for type: tests/test_abi_and_host.py, for every entry)
     # the _ctl steps are the plain ones with (grad_scale) / (step, grad_scale) replaced by one record pointer
     sgd, sgd_c = L.SIGNATURES["sodt_sgd_ema_step"], L.SIGNATURES["sodt_sgd_ema_step_ctl"]
     assert len(sgd) == 16 and sgd_c[:13] + sgd_c[14:] == sgd[:13] + sgd[14:] and sgd_c[13] is C.c_void_p

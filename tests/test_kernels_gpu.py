@@ -552,7 +552,7 @@ def test_frontend(ops, dev, dt, B, S):
     t = S // 4
     out = torch.zeros(B * t * t, 192, device=dev, dtype=dt)
     ir_plane = x_ir[:, 0]
-    ops.frontend_fwd(x_rgb, ir_plane, 3 * S * S, w, b, g, be, out, B, S)
+    ops.frontend_fwd(x_rgb, ir_plane, 3 * S * S, w, b, g, be, out, B, S, S)
     sdd = {k: v.double().requires_grad_(True) for k, v in sd.items()}
     x4 = torch.cat([x_rgb, x_ir[:, 0:1]], 1).double()
     r, gg, bb, ii = R.channel_embeds(sdd, x4)
@@ -561,9 +561,9 @@ def test_frontend(ops, dev, dt, B, S):
     dout = rnd((B * t * t, 192), dev, dt, 5)
     ref.backward(dout.float().double())
     # direct atomics (no workspace) and the two-stage reduction through a workspace (filled with junk: it need not be zeroed)
-    for ws in (None, torch.full((ops.frontend_bwd_workspace_bytes(B, S) // 4,), 7.0, device=dev)):
+    for ws in (None, torch.full((ops.frontend_bwd_workspace_bytes(B, S, S) // 4,), 7.0, device=dev)):
         dw, db, dg, dbe = torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(g), torch.zeros_like(be)
-        ops.frontend_bwd(x_rgb, ir_plane, 3 * S * S, w, b, g, be, dout, dw, db, dg, dbe, B, S, 1, ws)
+        ops.frontend_bwd(x_rgb, ir_plane, 3 * S * S, w, b, g, be, dout, dw, db, dg, dbe, B, S, S, ws=ws)
         for ci, c in enumerate("rgbi"):
             close(dw[ci], sdd[f"image_encoder.channel_embed_{c}.proj.weight"].grad.view(48, 16), dt, what=f"dw {c}")
             close(db[ci], sdd[f"image_encoder.channel_embed_{c}.proj.bias"].grad, dt, what=f"db {c}")
@@ -588,8 +588,8 @@ def test_cross_channel_attention_general(ops, dev, dt, ws, shift):
     M = B * t * t
     e = torch.zeros(M, 192, device=dev)
     out = torch.zeros(M, 192, device=dev, dtype=dt)
-    ops.patch_embed4_fwd(x_rgb, x_ir, 3 * S * S, w, b, e, B, S)
-    ops.cross_attn_ln_fwd(e, g, be, out, B, S, ws, shift)
+    ops.patch_embed4_fwd(x_rgb, x_ir, 3 * S * S, w, b, e, B, S, S)
+    ops.cross_attn_ln_fwd(e, g, be, out, B, S, S, ws, shift)
     sdd = {k: v.double().cpu() for k, v in sd.items()}      # oracle on the CPU (its mask helper builds CPU tensors)
     for ci, c in enumerate("rgbi"):
         sdd[f"image_encoder.channel_embed_{c}.proj.weight"] = (w[ci].double().cpu().view(48, 1, 4, 4))
@@ -603,8 +603,8 @@ def test_cross_channel_attention_general(ops, dev, dt, ws, shift):
     ref.backward(dout.float().double().cpu())
     de = torch.zeros(M, 192, device=dev)
     dw, db, dg, dbe = torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(g), torch.zeros_like(be)
-    ops.cross_attn_ln_bwd(e, g, dout, de, dg, dbe, B, S, ws, shift)
-    ops.patch_embed4_bwd(x_rgb, x_ir, 3 * S * S, de, dw, db, B, S)
+    ops.cross_attn_ln_bwd(e, g, dout, de, dg, dbe, B, S, S, ws, shift)
+    ops.patch_embed4_bwd(x_rgb, x_ir, 3 * S * S, de, dw, db, B, S, S)
     for ci, c in enumerate("rgbi"):
         close(dw[ci], sdd[f"image_encoder.channel_embed_{c}.proj.weight"].grad.view(48, 16), dt, what=f"dw {c}")
         close(db[ci], sdd[f"image_encoder.channel_embed_{c}.proj.bias"].grad, dt, what=f"db {c}")

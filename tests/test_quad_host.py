@@ -5,7 +5,6 @@ entries in the header and the binding."""
 import importlib
 import os
 import random
-import re
 
 import pytest
 import torch
@@ -105,9 +104,5 @@ def test_quad_targets_edges(P):
 
 
 def test_header_declares_and_lib_binds_the_entries(pkg):
-    src = open(os.path.join(ROOT, "include", "sodt_hip.h")).read()
-    declared = set(re.findall(r"^int\s+(sodt_\w+)\s*\(", src, flags=re.M))
-    lib = pkg._lib.load()
-    for name in ("sodt_quad_u8", "sodt_preprocess_u8_quad"):
-        assert name in declared and name in pkg._lib.SIGNATURES and hasattr(lib, name), name
+    # declared, exported and bound type for type: tests/test_abi_and_host.py, for every entry; the arities stay pinned here
     assert len(pkg._lib.SIGNATURES["sodt_quad_u8"]) == 11 and len(pkg._lib.SIGNATURES["sodt_preprocess_u8_quad"]) == 13

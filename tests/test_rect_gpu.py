@@ -1,4 +1,4 @@
-"""Rectangular inputs on the GPU: the front-end kernels on an H x W image (the ``_hw`` entry points) against the float64 oracle
+"""Rectangular inputs on the GPU: the front-end kernels on an H x W image against the float64 oracle
 pieces, the whole model at H != W against ``R.model_forward``, a training loop on a rectangular batch, the refusals, and that a
 square run issues exactly the launches it issued before.
 
@@ -60,7 +60,7 @@ def test_frontend_hw(ops, dev, dt, B, H, W):
     M = B * th * tw
     out = torch.zeros(M, 192, device=dev, dtype=dt)
     ir_plane = x_ir[:, 0]                               # one plane of a three-plane tensor: its own batch stride
-    ops.frontend_fwd_hw(x_rgb, ir_plane, 3 * H * W, w, b, g, be, out, B, H, W)
+    ops.frontend_fwd(x_rgb, ir_plane, 3 * H * W, w, b, g, be, out, B, H, W)
     sdd = {k: v.double().requires_grad_(True) for k, v in sd.items()}
     x4 = torch.cat([x_rgb, x_ir[:, 0:1]], 1).double()
     planes = R.channel_embeds(sdd, x4)
@@ -69,30 +69,11 @@ def test_frontend_hw(ops, dev, dt, B, H, W):
     close(out, ref, dt, what="frontend_hw fwd")
     dout = rnd((M, 192), dev, dt, 5)
     ref.backward(dout.float().double())
-    assert ops.frontend_bwd_hw_workspace_bytes(B, H, W) == ops.frontend_bwd_workspace_bytes(B, H)
-    for ws in (None, torch.full((ops.frontend_bwd_hw_workspace_bytes(B, H, W) // 4,), 7.0, device=dev)):
+    assert ops.frontend_bwd_workspace_bytes(B, H, W) == ops.frontend_bwd_workspace_bytes(B, H, H)
+    for ws in (None, torch.full((ops.frontend_bwd_workspace_bytes(B, H, W) // 4,), 7.0, device=dev)):
         dw, db, dg, dbe = torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(g), torch.zeros_like(be)
-        ops.frontend_bwd_hw(x_rgb, ir_plane, 3 * H * W, w, b, g, be, dout, dw, db, dg, dbe, B, H, W, 1, ws)
+        ops.frontend_bwd(x_rgb, ir_plane, 3 * H * W, w, b, g, be, dout, dw, db, dg, dbe, B, H, W, ws=ws)
         _check_param_grads(sdd, dw, db, dg, dbe, dt)
-
-
-@pytest.mark.parametrize("dt", DTYPES)
-def test_hw_entries_on_a_square_are_the_square_entries(ops, dev, dt):
-    B, S = 2, 96
-    _, w, b, g, be = _fe_params(dev)
-    x_rgb, x_ir = (t.to(dev) for t in _inputs(B, S, S, seed=4))
-    M = B * (S // 4) ** 2
-    a, c = torch.zeros(M, 192, device=dev, dtype=dt), torch.zeros(M, 192, device=dev, dtype=dt)
-    ops.frontend_fwd(x_rgb, x_ir[:, 0], 3 * S * S, w, b, g, be, a, B, S)
-    ops.frontend_fwd_hw(x_rgb, x_ir[:, 0], 3 * S * S, w, b, g, be, c, B, S, S)
-    assert torch.equal(a, c)
-    ea, ec = torch.zeros(M, 192, device=dev), torch.zeros(M, 192, device=dev)
-    ops.patch_embed4_fwd(x_rgb, x_ir, 3 * S * S, w, b, ea, B, S)
-    ops.patch_embed4_fwd_hw(x_rgb, x_ir, 3 * S * S, w, b, ec, B, S, S)
-    assert torch.equal(ea, ec)
-    ops.cross_attn_ln_fwd(ea, g, be, a, B, S, 4, 2)
-    ops.cross_attn_ln_fwd_hw(ea, g, be, c, B, S, S, 4, 2)
-    assert torch.equal(a, c)
 
 
 @pytest.mark.parametrize("dt", DTYPES)
@@ -106,8 +87,8 @@ def test_cross_channel_attention_general_hw(ops, dev, dt, ws, shift):
     M = B * (H // 4) * (W // 4)
     e = torch.zeros(M, 192, device=dev)
     out = torch.zeros(M, 192, device=dev, dtype=dt)
-    ops.patch_embed4_fwd_hw(x_rgb, x_ir, 3 * H * W, w, b, e, B, H, W)
-    ops.cross_attn_ln_fwd_hw(e, g, be, out, B, H, W, ws, shift)
+    ops.patch_embed4_fwd(x_rgb, x_ir, 3 * H * W, w, b, e, B, H, W)
+    ops.cross_attn_ln_fwd(e, g, be, out, B, H, W, ws, shift)
     sdd = {k: v.double().cpu().requires_grad_(True) for k, v in sd.items()}      # oracle on the CPU (its mask helper builds CPU tensors)
     x4 = torch.cat([x_rgb, x_ir[:, 0:1]], 1).double().cpu()
     planes = R.channel_embeds(sdd, x4)
@@ -118,8 +99,8 @@ def test_cross_channel_attention_general_hw(ops, dev, dt, ws, shift):
     ref.backward(dout.float().double().cpu())
     de = torch.zeros(M, 192, device=dev)
     dw, db, dg, dbe = torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(g), torch.zeros_like(be)
-    ops.cross_attn_ln_bwd_hw(e, g, dout, de, dg, dbe, B, H, W, ws, shift)
-    ops.patch_embed4_bwd_hw(x_rgb, x_ir, 3 * H * W, de, dw, db, B, H, W)
+    ops.cross_attn_ln_bwd(e, g, dout, de, dg, dbe, B, H, W, ws, shift)
+    ops.patch_embed4_bwd(x_rgb, x_ir, 3 * H * W, de, dw, db, B, H, W)
     _check_param_grads(sdd, dw, db, dg, dbe, dt)
 
 
@@ -134,23 +115,23 @@ def test_hw_entries_refuse_without_touching_their_outputs(ops, dev):
     dout = torch.ones(8 * 12, 192, device=dev)
     for H, W in ((30, 48), (32, 46)):
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.frontend_fwd_hw(x, x[:, 0], 3 * 32 * 48, w, b, g, be, out, 1, H, W)
+            ops.frontend_fwd(x, x[:, 0], 3 * 32 * 48, w, b, g, be, out, 1, H, W)
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.frontend_bwd_hw(x, x[:, 0], 3 * 32 * 48, w, b, g, be, dout, *grads, 1, H, W)
+            ops.frontend_bwd(x, x[:, 0], 3 * 32 * 48, w, b, g, be, dout, *grads, 1, H, W)
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.patch_embed4_fwd_hw(x, x, 3 * 32 * 48, w, b, e, 1, H, W)
+            ops.patch_embed4_fwd(x, x, 3 * 32 * 48, w, b, e, 1, H, W)
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.patch_embed4_bwd_hw(x, x, 3 * 32 * 48, dout, grads[0], grads[1], 1, H, W)
+            ops.patch_embed4_bwd(x, x, 3 * 32 * 48, dout, grads[0], grads[1], 1, H, W)
     ok = torch.zeros(8 * 12, 192, device=dev)
     for ws in (8, 3):                                    # tw = 12 is no multiple of 8; th = 8 is no multiple of 3
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.cross_attn_ln_fwd_hw(ok, g, be, out, 1, 32, 48, ws, 0)
+            ops.cross_attn_ln_fwd(ok, g, be, out, 1, 32, 48, ws, 0)
         with pytest.raises(RuntimeError, match="status 1"):
-            ops.cross_attn_ln_bwd_hw(ok, g, dout, e, grads[2], grads[3], 1, 32, 48, ws, 0)
+            ops.cross_attn_ln_bwd(ok, g, dout, e, grads[2], grads[3], 1, 32, 48, ws, 0)
     torch.cuda.synchronize()
     for t in [out, e] + grads:
         assert bool(torch.isnan(t).all())
-    ops.cross_attn_ln_fwd_hw(ok, g, be, out, 1, 32, 48, 4, 0)          # and the grid both sides divide is accepted
+    ops.cross_attn_ln_fwd(ok, g, be, out, 1, 32, 48, 4, 0)          # and the grid both sides divide is accepted
     torch.cuda.synchronize()
     assert bool(torch.isfinite(out).all())
 
@@ -371,7 +352,7 @@ def test_a_square_run_keeps_its_launch_names_and_plan_key(ops, dev):
     eng = model._get_engine()
     assert list(eng.plans) == [(2, 128, torch.float32, True, 0)]
     assert eng.plans[(2, 128, torch.float32, True)].S == 128
-    # and a rectangle takes the _hw entries, in the same places
+    # and a rectangle goes through the same entries (they take H and W), under a plan key of its own
     names.clear()
     ops._launch = spy
     try:
@@ -380,6 +361,6 @@ def test_a_square_run_keeps_its_launch_names_and_plan_key(ops, dev):
         pred[0].square().mean().backward()
     finally:
         ops._launch = real
-    assert "sodt_frontend_fwd_hw" in names and "sodt_frontend_bwd_hw" in names
-    assert "sodt_frontend_fwd" not in names and "sodt_frontend_bwd" not in names
+    assert "sodt_frontend_fwd" in names and "sodt_frontend_bwd" in names
+    assert not any(n.endswith("_hw") for n in names), [n for n in names if n.endswith("_hw")]
     assert (1, (256, 128), torch.float32, True, 0) in eng.plans

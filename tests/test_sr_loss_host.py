@@ -1,5 +1,5 @@
-"""Host-side checks of the --super loss term (no GPU): the three C entries of csrc/srloss.hip are declared in the header, exported
-by the library and bound; the constants agree with the header; SRLoss names each bad input in a ValueError before anything
+"""Host-side checks of the --super loss term (no GPU): forward and backward of csrc/srloss.hip share their leading
+arguments; the constants agree with the header; SRLoss names each bad input in a ValueError before anything
 reaches the library; the entries themselves refuse bad arguments before a launch (exercised with host memory); and the
 two-FMA form of float(k) / 255.0f the kernels use equals the IEEE quotient for every byte value."""
 import ctypes as C
@@ -13,17 +13,11 @@ import torch
 
 PKG = "small-object-detection-transformers_amd"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("sodt_sr_l1_workspace_bytes", "sodt_sr_l1_fwd", "sodt_sr_l1_bwd")
 
 
 def test_entries_declared_exported_and_bound(pkg, ops):
-    L = pkg._lib
-    lib = L.load()
+    L = pkg._lib                    # (declared, exported, bound type for type: tests/test_abi_and_host.py, for every entry)
     hdr = open(os.path.join(ROOT, "include", "sodt_hip.h")).read()
-    for name in NEW:
-        assert re.search(rf"^int\s+{name}\s*\(", hdr, flags=re.M), f"{name} is not declared in include/sodt_hip.h"
-        assert name in L.SIGNATURES and name in L.exported_symbols()
-        assert hasattr(lib, name), f"{name} is not exported by libsodt_hip.so"
     assert "Train.py:420-427" in hdr
     define = lambda n: int(re.search(rf"#define\s+{n}\s+(\d+)", hdr).group(1))
     assert define("SODT_U8") == L.U8 and define("SODT_F32") == L.F32

@@ -29,13 +29,13 @@ def main():
     t = a.S // 4
     irp = ir[:, 0]
     y = torch.zeros(a.B * t * t, 192, device=dev, dtype=dt)
-    ops.frontend_fwd(rgb, irp, a.S * a.S, w, b, gam, bet, y, a.B, a.S)
+    ops.frontend_fwd(rgb, irp, a.S * a.S, w, b, gam, bet, y, a.B, a.S, a.S)
     dy = torch.randn_like(y)
-    wsb = torch.empty(ops.frontend_bwd_workspace_bytes(a.B, a.S) // 4, device=dev)
+    wsb = torch.empty(ops.frontend_bwd_workspace_bytes(a.B, a.S, a.S) // 4, device=dev)
     dw, db, dg, dbe = torch.zeros_like(w), torch.zeros_like(b), torch.zeros_like(gam), torch.zeros_like(bet)
-    for name, fn in (("fwd", lambda: ops.frontend_fwd(rgb, irp, a.S * a.S, w, b, gam, bet, y, a.B, a.S)),
-                     ("bwd", lambda: ops.frontend_bwd(rgb, irp, a.S * a.S, w, b, gam, bet, dy, dw, db, dg, dbe, a.B, a.S)),
-                     ("bwd+ws", lambda: ops.frontend_bwd(rgb, irp, a.S * a.S, w, b, gam, bet, dy, dw, db, dg, dbe, a.B, a.S, 1, wsb))):
+    for name, fn in (("fwd", lambda: ops.frontend_fwd(rgb, irp, a.S * a.S, w, b, gam, bet, y, a.B, a.S, a.S)),
+                     ("bwd", lambda: ops.frontend_bwd(rgb, irp, a.S * a.S, w, b, gam, bet, dy, dw, db, dg, dbe, a.B, a.S, a.S)),
+                     ("bwd+ws", lambda: ops.frontend_bwd(rgb, irp, a.S * a.S, w, b, gam, bet, dy, dw, db, dg, dbe, a.B, a.S, a.S, ws=wsb))):
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
