@@ -832,6 +832,50 @@ int sodt_kmeans_lloyd_workspace_bytes(long N, int R, int n, size_t* bytes);
 int sodt_kmeans_lloyd(const double* obs, long N, double* books, int* alive, double* prev, int* done, int R, int n,
                       double thresh, int iters, void* ws, size_t ws_bytes, sodt_stream_t st);
 
+/* ---- --image-weights (Train.py:335-341; basics/utils/general.py: labels_to_class_weights :220-236, labels_to_image_weights
+ *      :239-244; random.choices), once per epoch (csrc/sampling.hip) ----
+ * status: one int32 on the device that the entries OR the SODT_SAMPLING_* bits into; the caller zeroes it.
+ * sodt_class_counts: the np.bincount of :227 and :241 for all images at once.  cls, img: (M) int32, the class and the image
+ *   id of every label.  One thread per label (a grid-stride loop beyond 262,144 labels) adds 1 to counts[img][cls], (n_img, nc)
+ *   int32, and to class_total[cls], (nc) int64, with integer atomics - exact in any order; the caller zeroes both.  Up to
+ *   nc = 1024 a block gathers its class totals in LDS and adds each once; above that every label adds to class_total.  A class
+ *   outside [0, nc) or an image id outside [0, n_img) sets its status bit and is not counted.  M == 0 launches nothing.
+ *   0 <= M < 2^31, 1 <= n_img <= 2^24, 1 <= nc <= 65536.
+ * sodt_image_weights: iw[i] = sum over c of cw[c] * counts[i][c] (:242), f64: ONE accumulator per image that starts at +0.0
+ *   and takes the classes in ascending order, each product rounded before it is added (no fused multiply-add, no atomics).
+ *   Rows of `counts` are read as runs of up to 32 classes through LDS.
+ * sodt_weighted_choices: `random.choices(range(n), weights=iw, k=k)` from k uniform numbers u (k) f64 in [0, 1), the values
+ *   random.random() returned in draw order.  cum: (n) f64, an output (it may follow the workspace in one allocation): the
+ *   inclusive prefix sums of iw.  Their association order depends on n alone and no atomic is used, so equal inputs give
+ *   equal bits on every call.  With W = SODT_CHOICES_BLOCK = 1024 and iw padded with +0.0 to a multiple of W:
+ *     phase 1, one block of 256 threads per W weights: thread t takes the 4 consecutive weights a0..a3 from 4 t,
+ *       s0 = a0, s_j = s_(j-1) + a_j.  The 256 thread sums s3 are scanned (`block scan`): within each wave of 64 lanes
+ *       by Hillis-Steele, v[l] = v[l] + v[l - o] for all l >= o at once, o = 1, 2, 4, 8, 16, 32; the wave sums W0..W3 (lane 63)
+ *       give the wave prefixes 0.0, W0, W0 + W1, (W0 + W1) + W2 and the block sum ((W0 + W1) + W2) + W3; the exclusive prefix of
+ *       thread t is wave_prefix + (lane > 0 ? v[lane - 1] : 0.0).  local[4 t + j] = prefix_t + s_j.
+ *     phase 2, ONE block: the nb = ceil(n / W) block sums, padded with +0.0 to 256 * per, per = ceil(nb / 256); thread t takes
+ *       the `per` consecutive sums from t * per serially as above, the thread sums go through the same block scan, and
+ *       inclusive[t * per + j] = prefix_t + s_j.  offset[0] = 0.0, offset[b + 1] = inclusive[b].
+ *     phase 3: cum[e] = offset[e / W] + local[e].
+ *   total = cum[n - 1].  total <= 0: SODT_SAMPLING_ZERO_TOTAL; otherwise total NaN or infinite: SODT_SAMPLING_NONFINITE_TOTAL;
+ *   in both cases every idx is -1.  Otherwise draw j forms x = u[j] * total (one IEEE multiply) and idx[j] = the number of
+ *   entries of cum[0 .. n-2] that are <= x, i.e. Python's bisect_right(cum, x, 0, n - 1): an x that equals a boundary goes
+ *   right, an image of weight zero is never drawn, and the result is at most n - 1.  idx: (k) int32.  1 <= n <= 2^24,
+ *   0 <= k <= 2^24.  ws: 16-byte aligned, at least sodt_weighted_choices_workspace_bytes(n, k).
+ * SODT_EINVAL, nothing launched or written: a null or misaligned pointer (4 bytes for int32, 8 for int64 and f64, 16 for ws),
+ * a size outside the above, ws too small.  No entry allocates, synchronises or reads the environment. */
+#define SODT_CHOICES_BLOCK 1024
+#define SODT_SAMPLING_BAD_CLASS 1
+#define SODT_SAMPLING_BAD_IMAGE 2
+#define SODT_SAMPLING_ZERO_TOTAL 4
+#define SODT_SAMPLING_NONFINITE_TOTAL 8
+int sodt_class_counts(const int* cls, const int* img, long M, int n_img, int nc, int* counts, long long* class_total,
+                      int* status, sodt_stream_t st);
+int sodt_image_weights(const int* counts, const double* cw, int n_img, int nc, double* iw, sodt_stream_t st);
+int sodt_weighted_choices_workspace_bytes(int n, int k, size_t* bytes);
+int sodt_weighted_choices(const double* iw, int n, const double* u, int k, int* idx, double* cum, int* status, void* ws,
+                          size_t ws_bytes, sodt_stream_t st);
+
 /* hipMemsetAsync(p, 0, bytes) on the stream (statistics / gradient accumulators) */
 int sodt_memset_zero(void* p, long bytes, sodt_stream_t st);
 

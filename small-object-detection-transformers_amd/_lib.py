@@ -31,6 +31,8 @@ EPI_BIAS, EPI_RESID, EPI_GELU_DUAL, EPI_DGELU = 1, 2, 4, 8
 EPI_STATS, EPI_AFFINE_SILU, EPI_DETECT, EPI_OUT_F32 = 16, 32, 64, 128
 EPI_GELU, EPI_DGELU_RC, EPI_RELU, EPI_DRELU = 256, 512, 2048, 4096      # (1024: retired, see include/sodt_hip.h)
 DETECT_NO_WGRAD, DETECT_NO_DX = 1, 2                  # SODT_DETECT_NO_WGRAD / SODT_DETECT_NO_DX
+CHOICES_BLOCK = 1024                                  # SODT_CHOICES_BLOCK: weights per block of sodt_weighted_choices' scan
+SAMPLING_BAD_CLASS, SAMPLING_BAD_IMAGE, SAMPLING_ZERO_TOTAL, SAMPLING_NONFINITE_TOTAL = 1, 2, 4, 8     # SODT_SAMPLING_*
 STATS_REPL = 16      # SODT_STATS_REPL: replicas of the [2][N] f64 BatchNorm statistics buffer
 
 
@@ -215,6 +217,11 @@ SIGNATURES = {
     "sodt_anchor_evolve": [_P, _L, _F, _P, _I, _P, _P, _I, _P, _P, C.c_size_t, _P],
     "sodt_kmeans_lloyd_workspace_bytes": [_L, _I, _I, C.POINTER(C.c_size_t)],
     "sodt_kmeans_lloyd": [_P, _L, _P, _P, _P, _P, _I, _I, C.c_double, _I, _P, C.c_size_t, _P],
+    # Train.py:335-341 / general.py:220-244 (csrc/sampling.hip)
+    "sodt_class_counts": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
+    "sodt_image_weights": [_P, _P, _I, _I, _P, _P],
+    "sodt_weighted_choices_workspace_bytes": [_I, _I, C.POINTER(C.c_size_t)],
+    "sodt_weighted_choices": [_P, _I, _P, _I, _P, _P, _P, _P, C.c_size_t, _P],
     "sodt_bilinear_up2_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sodt_bilinear_up2_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "sodt_pixel_shuffle2": [_P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -23,7 +23,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # multiply-adds whatever `#pragma clang fp contract(off)` says, so a file that must reproduce the reference's rounding
 # bit for bit is compiled with contraction off.
 SOURCE_FLAGS = {"metrics.hip": ["-ffp-contract=off"], "wbf.hip": ["-ffp-contract=off"], "autoanchor.hip": ["-ffp-contract=off"],
-                "nms_batch.hip": ["-ffp-contract=off"]}
+                "nms_batch.hip": ["-ffp-contract=off"], "sampling.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

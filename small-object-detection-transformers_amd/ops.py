@@ -910,6 +910,33 @@ def kmeans_lloyd(obs, books, alive, prev, done, thresh, iters, ws):
             int(iters), _p(ws), ws.numel() * ws.element_size())
 
 
+CHOICES_BLOCK = L.CHOICES_BLOCK         # weights per block of the scan of weighted_choices (SODT_CHOICES_BLOCK)
+CLASS_COUNTS_GRID = 1024 * 256          # labels that one grid of class_counts covers with one thread each
+
+
+def class_counts(cls, img, n_img, nc, counts, class_total, status):
+    """np.bincount per image and overall (general.py:227, :241): cls, img (M) int32; counts (n_img, nc) int32 and class_total
+    (nc) int64 are ADDED to, status (1) int32 gets SODT_SAMPLING_BAD_* ORed in - the caller zeroes all three."""
+    _launch("sodt_class_counts", _p(cls), _p(img), cls.numel(), int(n_img), int(nc), _p(counts), _p(class_total), _p(status))
+
+
+def image_weights(counts, cw, iw):
+    """iw[i] = sum_c cw[c] * counts[i][c] in f64, classes ascending (general.py:242): counts (n_img, nc) int32, cw (nc) f64."""
+    n_img, nc = counts.shape
+    _launch("sodt_image_weights", _p(counts), _p(cw), n_img, nc, _p(iw))
+
+
+def weighted_choices_workspace_bytes(n: int, k: int) -> int:
+    return _ws_bytes("sodt_weighted_choices_workspace_bytes", int(n), int(k))
+
+
+def weighted_choices(iw, u, idx, cum, status, ws):
+    """random.choices(range(n), weights=iw, k=k) from the k uniform numbers u: iw, cum (n) f64, u (k) f64, idx (k) int32,
+    status (1) int32 (SODT_SAMPLING_*_TOTAL are ORed in), all on the device; no host read."""
+    _launch("sodt_weighted_choices", _p(iw), iw.numel(), _p(u), u.numel(), _p(idx), _p(cum), _p(status), _p(ws),
+            ws.numel() * ws.element_size())
+
+
 def maxpool5_fwd(x, y, argmax, B, H, W, Cc, ldx=None, ldy=None, x_off=0, y_off=0):
     """y = MaxPool2d(5, 1, 2)(x), token-major; x / y may be channel slices of wider tensors (ld*, *_off in elements)."""
     es = x.element_size()
