@@ -708,6 +708,46 @@ int sodt_adam_ema_step_ctl(float* p, const float* g, float* exp_avg, float* exp_
                            const double* beta1, const double* beta2, const double* eps, const double* weight_decay,
                            int decoupled, const sodt_step_ctl* ctl, float ema_decay, sodt_stream_t st);
 
+/* Sharpness-aware minimisation around the fused steps (csrc/sam.hip): basics/utils/sam.py over the same flat f32 buffers and
+ * the same group_of_chunk map (4-element chunks, ngroups <= 4, chunks marked 255 are not owned: never measured, never
+ * written, in p, old_p and the mirror alike).  rho (floats) and adaptive (ints, non-zero = set) are host arrays of ngroups.
+ * A map byte in [ngroups, 4) names no group of the call: its chunk enters the norm unweighted and is perturbed with rho 0, that
+ * is, left where it is (old_p and the mirror are still written for it).
+ * The three entries share a 64-byte record in device memory (16-byte aligned), passed as a double* because it is eight
+ * 8-byte words; no C type is declared for it:
+ *   offset  0  double    acc_sumsq   work words of sodt_sam_norm: the entry zeroes these 16 bytes before its launch,
+ *           8  unsigned  acc_found   blocks touch them with device-scope atomics only
+ *          12  unsigned  ticket
+ *          16  double    sumsq       sum over the owned elements of (w * g)^2, g as stored (still scaled), accumulated in f64
+ *          24  double    norm        sqrt(sumsq) * |inv_scale|: the norm sam.py:49-59 forms, of the unscaled gradient
+ *          32  double    inv         found ? 0 : 1 / (norm + 1e-12)      (sam.py:18: rho / (grad_norm + 1e-12), without rho)
+ *          40  float     found       1 if an owned gradient element is inf / NaN or the norm is not finite, else 0
+ *          44  float     inv_scale   (float)(grad_scale / scale): what the perturbation multiplies the stored gradient by
+ *          48  int       reserved[4] */
+
+/* sam.py:49-59 (SAM._grad_norm: one norm per tensor, stacked, and a norm of those) in one pass: w = |p| for a group whose
+ * adaptive flag is set, else 1; the last block to finish finalises *rec.  p is read only if some group is adaptive and may be
+ * null otherwise.  scale is a DEVICE pointer to one f32 (GradScaler's scale tensor) or null = 1; 1 / scale is formed as in
+ * sodt_grad_stats and grad_scale, the host factor, composes by multiplication.  SODT_EINVAL (nothing is touched): null or
+ * misaligned (16 bytes) g or rec, a misaligned p, p null with an adaptive group, null adaptive, misaligned scale (4 bytes),
+ * n_elems % 4, ngroups outside 1..4, a NaN grad_scale. */
+int sodt_sam_norm(const float* p, const float* g, const unsigned char* group_of_chunk, long n_elems, int ngroups,
+                  const int* adaptive, const float* scale, float grad_scale, double* rec, sodt_stream_t st);
+
+/* sam.py:19-25 (SAM.first_step's loop: old_p = p.data.clone(); e_w = (p^2 if adaptive else 1) * p.grad * scale; p.add_(e_w))
+ * in one pass over the owned chunks:
+ *   old_p = p;   p += (adaptive ? p*p : 1) * g * rec.inv_scale * (rho[group] * rec.inv);   p_cast = (cast_dtype) p
+ * rec is a DEVICE pointer that a sodt_sam_norm call earlier on the same stream has filled.  p_cast (the run-dtype mirror) is
+ * nullable.  With rec.found set, p stays bit for bit what it was; old_p = p and the cast are still written.  SODT_EINVAL
+ * (nothing is touched): null or misaligned (16 bytes) p, g, old_p or rec, a misaligned p_cast, n_elems % 4, ngroups outside
+ * 1..4, null rho / adaptive, a negative or NaN rho, an unknown cast_dtype. */
+int sodt_sam_perturb(float* p, const float* g, float* old_p, void* p_cast, int cast_dtype, const unsigned char* group_of_chunk,
+                     long n_elems, int ngroups, const float* rho, const int* adaptive, const double* rec, sodt_stream_t st);
+
+/* sam.py:30-34 (SAM.second_step's loop: p.data = old_p) as a copy into the flat buffer, owned chunks only; the step that
+ * follows rewrites the mirror.  SODT_EINVAL: null or misaligned (16 bytes) p or old_p, n_elems % 4. */
+int sodt_sam_restore(float* p, const float* old_p, const unsigned char* group_of_chunk, long n_elems, sodt_stream_t st);
+
 /* Input pre-processing of the training / evaluation loop (csrc/preprocess.hip): `imgs.to(device).float() / 255.0` followed by
  * `F.interpolate(image, size=[i // down_factor ...], mode='bilinear', align_corners=True)` (Train.py:364-374; test.py:124-129
  * is the factor-1 case) for the RGB and the IR batch in one launch.  rgb / ir: uint8 (B, c, Hin, Win) contiguous (device);

@@ -107,6 +107,13 @@ class StepCtl(C.Structure):
                 ("reserved", C.c_int * 2)]
 
 
+# the 64-byte record of sodt_sam_norm / _perturb (include/sodt_hip.h documents it; the header declares no C type for it):
+# field -> (byte offset, ctypes type)
+SAM_REC_BYTES = 64
+SAM_REC = {"acc_sumsq": (0, C.c_double), "acc_found": (8, C.c_uint), "ticket": (12, C.c_uint), "sumsq": (16, C.c_double),
+           "norm": (24, C.c_double), "inv": (32, C.c_double), "found": (40, C.c_float), "inv_scale": (44, C.c_float)}
+
+
 TTA_MAX_PASSES = 4                                    # SODT_TTA_MAX_PASSES
 
 
@@ -204,6 +211,10 @@ SIGNATURES = {
                               C.POINTER(C.c_float), _I, _P, _F, _P],
     "sodt_adam_ema_step_ctl": [_P, _P, _P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _F, _P],
+    # basics/utils/sam.py (csrc/sam.hip); the 64-byte record goes down as a plain pointer (SAM_REC names its words)
+    "sodt_sam_norm": [_P, _P, _P, _L, _I, _P, _P, _F, _P, _P],
+    "sodt_sam_perturb": [_P, _P, _P, _P, _I, _P, _L, _I, C.POINTER(C.c_float), _P, _P, _P],
+    "sodt_sam_restore": [_P, _P, _P, _L, _P],
     "sodt_preprocess_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_preprocess_u8_ms": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_quad_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_ulonglong, _P],

@@ -66,6 +66,7 @@ class Plan:
         self.enc_bwd_start: Optional[int] = None  # index in bwd_main where the head's backward ends and the encoder's begins
         self.enc_gin: Optional[list] = None       # [(buf, ld, off, c)]: where the head leaves d(f0), d(f1), d(f2)
         self.det_fused: Optional[bool] = None     # Detect's backward is the live one-pass launch, not part of bwd_main (set with bwd_main)
+        self.bn_marks: List[list] = []            # [index in fwd_main, BatchNorm2d, its name, momentum recorded] of every sodt_bn_finalize
 
     def unit(self, name):
         """the freeze.UnitRecord of unit `name`"""
@@ -646,6 +647,7 @@ class Engine:
                 self._forward_main(plan, P)
             plan.fwd_main = rec.calls
         else:
+            self._sync_bn_momentum(plan)
             self._replay(plan, "fwd_main", plan.fwd_main, self.probes_fwd)
         # (4) Detect: live (fresh output tensor every call)
         pred = torch.empty(B, self.na, th, tw, self.no, device=self.dev, dtype=torch.float32)
@@ -655,6 +657,44 @@ class Engine:
                 and ops.detect_fwd(hx, wd, bd, pred, B, th * tw, self.na, self.no, hc)):
             ops.gemm_nt([SegSpec(hx)], wd, pred, T1, self.na * self.no, hc, bias=bd, detect=(self.na, self.no, th * tw))
         return pred
+
+    @staticmethod
+    def _bn_momentum(bn, name):
+        """bn.momentum as sodt_bn_finalize takes it (bypass_bn.disable_running_stats sets 0: the running statistics stand still)"""
+        m = bn.momentum
+        if m is None:
+            raise NotImplementedError(f"{name}: BatchNorm2d(momentum=None), the cumulative moving average, is not built")
+        return float(m)
+
+    def _sync_bn_momentum(self, plan: Plan):
+        """Every Conv's bn.momentum is read at every training forward: a recorded sodt_bn_finalize whose BatchNorm2d has
+        another momentum now than at its recording is re-recorded with the new one (its last argument).  A hipGraph captured
+        from the list holds the arguments of its capture, so it is set aside under the momenta it was captured with and taken
+        back when they return (bypass_bn alternates between two sets: one capture each, nothing re-captured per step and no
+        graph destroyed while a replay of it may still run)."""
+        was_sig = None
+        for mk in plan.bn_marks:
+            idx, bn, name, was = mk
+            if bn.momentum != was:
+                m = self._bn_momentum(bn, name)
+                if was_sig is None:
+                    was_sig = tuple(k[3] for k in plan.bn_marks)
+                fn, args, cname, tag = plan.fwd_main[idx]
+                assert cname == "sodt_bn_finalize", cname
+                plan.fwd_main[idx] = (fn, args[:-1] + (C.c_float(m),), cname, tag)
+                mk[3] = m
+        if was_sig is None or not any(k == "fwd_main" or (isinstance(k, tuple) and k[0] == "fwd_main") for k in plan.graphs):
+            return
+        g = plan.graphs.pop("fwd_main", None)
+        if g is not None:
+            kept = [k for k in plan.graphs if isinstance(k, tuple) and k[0] == "fwd_main"]
+            if len(kept) >= 4:              # a momentum that keeps moving: let the oldest capture go, once nothing can be replaying it
+                torch.cuda.current_stream().synchronize()
+                del plan.graphs[kept[0]]
+            plan.graphs[("fwd_main", was_sig)] = g
+        g = plan.graphs.pop(("fwd_main", tuple(k[3] for k in plan.bn_marks)), None)
+        if g is not None:
+            plan.graphs["fwd_main"] = g
 
     def _replay(self, plan: Plan, key: str, calls, probes):
         """Re-issue a recorded launch list.  With SODT_HIPGRAPH=1 (single-process runs without probes) the list is captured
@@ -1119,7 +1159,12 @@ class Engine:
                 ops.col_stats(z, stats, M, Cout)
             else:
                 ops.gemm_nt(segs, w[wname], z, M, Cout, K, spatial=spatial, stats=stats)
-            ops.bn_finalize(stats, mr, bufs[pname + "bn.running_mean"], bufs[pname + "bn.running_var"], M, Cout, 1e-3, 0.03)
+            bn = self.model.get_submodule(pname + "bn")
+            mom = self._bn_momentum(bn, pname + "bn")      # (common.py's 0.03 unless somebody moved it: bypass_bn)
+            at = ops.recorded_count()
+            if at is not None:
+                plan.bn_marks.append([at, bn, pname + "bn", mom])
+            ops.bn_finalize(stats, mr, bufs[pname + "bn.running_mean"], bufs[pname + "bn.running_var"], M, Cout, 1e-3, mom)
             ops.bn_silu_fwd(z, mr, p[pname + "bn.weight"], p[pname + "bn.bias"], y, ldy, M, Cout)
         else:
             mr = plan.buf(tag + ".mr", (2, Cout), torch.float32)

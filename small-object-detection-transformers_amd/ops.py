@@ -852,6 +852,48 @@ def adam_ema_step_ctl(p, g, exp_avg, exp_avg_sq, ema, p_cast, group_of_chunk, lr
             int(bool(decoupled)), _p(ctl), C.c_float(ema_decay))
 
 
+def new_sam_rec(dev):
+    """A zeroed record of sam_norm / sam_perturb in device memory as eight f64 words (L.SAM_REC names the fields)."""
+    return torch.zeros(L.SAM_REC_BYTES // 8, dtype=torch.float64, device=dev)
+
+
+def sam_rec_field(rec, name):
+    """A one-element view of field `name` of a record made by new_sam_rec (no copy, no synchronisation)."""
+    off, ct = L.SAM_REC[name]
+    dt = {C.c_double: torch.float64, C.c_float: torch.float32, C.c_uint: torch.int32}[ct]
+    i = off // C.sizeof(ct)
+    return rec.view(dt)[i:i + 1]
+
+
+def _sam_flags(adaptive):
+    return (C.c_int * len(adaptive))(*[int(bool(a)) for a in adaptive])
+
+
+def sam_norm(p, g, group_of_chunk, adaptive, rec, scale=None, grad_scale=1.0):
+    """basics/utils/sam.py:49-59 in one pass over the flat gradient (csrc/sam.hip): the f64 norm of (|p| if adaptive else 1) * g
+    over the owned chunks, the not-finite flag and 1 / (norm + 1e-12) left in the device record `rec`.  `adaptive`: one flag
+    per group; `p` may be None when none is set.  `scale`: a one-element f32 DEVICE tensor (GradScaler's) or None."""
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != g.device):
+        raise TypeError("sam_norm: scale must be a one-element float32 tensor on the gradient's device")
+    _launch("sodt_sam_norm", _p(p), _p(g), _p(group_of_chunk), g.numel(), len(adaptive), _sam_flags(adaptive), _p(scale),
+            C.c_float(grad_scale), _p(rec))
+
+
+def sam_perturb(p, g, old_p, p_cast, group_of_chunk, rho, adaptive, rec):
+    """basics/utils/sam.py:19-25 in one pass: old_p = p, p += (p*p if adaptive else 1) * g * inv_scale * rho[group] / norm with
+    the norm read from `rec` (sam_norm), and the run-dtype mirror of the moved p (p_cast, nullable)."""
+    ng = len(rho)
+    assert len(adaptive) == ng
+    code = L.F32 if p_cast is None else dt_code(p_cast)
+    _launch("sodt_sam_perturb", _p(p), _p(g), _p(old_p), _p(p_cast), code, _p(group_of_chunk), p.numel(), ng,
+            (C.c_float * ng)(*[float(x) for x in rho]), _sam_flags(adaptive), _p(rec))
+
+
+def sam_restore(p, old_p, group_of_chunk):
+    """basics/utils/sam.py:34: p = old_p on the owned chunks."""
+    _launch("sodt_sam_restore", _p(p), _p(old_p), _p(group_of_chunk), p.numel())
+
+
 def sr_l1_workspace_bytes(B: int, C_: int, H: int, W: int) -> int:
     return _ws_bytes("sodt_sr_l1_workspace_bytes", int(B), int(C_), int(H), int(W), hint="B * C <= 65535, H * W < 2^31")
 

@@ -29,6 +29,10 @@ on this path.  With neither option and no scaler, ``step()`` is the one launch i
 
 Data parallel: ``ddp.attach`` all-reduces the flat gradient before the step, so every rank sees the same gradient and
 takes the same skip and clip decisions; no collective is added for them.
+
+``FusedSAM`` wraps either of them with the reference's sharpness-aware steps (basics/utils/sam.py: ``first_step`` /
+``second_step`` / ``step(closure)``): the gradient norm and the perturbation with its ``old_p`` copy and mirror are two launches,
+the restore a third, and the base optimizer's step runs unchanged after it (csrc/sam.hip).
 """
 from __future__ import annotations
 
@@ -314,3 +318,142 @@ class FusedAdam(_FusedOptimizer):
             self._bind()
             self._state[0].copy_(m.to(self._state[0].device))
             self._state[1].copy_(v.to(self._state[1].device))
+
+
+class FusedSAM(torch.optim.Optimizer):
+    """Sharpness-aware minimisation (basics/utils/sam.py: ``SAM.first_step`` / ``second_step`` / ``step(closure)``) around
+    ``FusedSGD`` or ``FusedAdam``, over the engine's flat buffers (csrc/sam.hip).  The constructor mirrors the reference's,
+    with the model the fused optimizers need::
+
+        FusedSAM(params, base_optimizer, model, rho=0.05, adaptive=False, **kwargs)
+
+    ``base_optimizer`` is the CLASS; it is built on this optimizer's ``param_groups`` with ``**kwargs`` (``lr``, ``momentum``,
+    ``ema=``, ``max_grad_norm=``, ``skip_nonfinite=`` ...), and the groups are shared: ``rho`` and ``adaptive`` are per-group
+    keys read at every call, next to the base's own.
+
+    ``first_step`` is two launches - ``sodt_sam_norm`` (the f64 norm of the owned gradient and a not-finite flag, left in a
+    device record) and ``sodt_sam_perturb`` (``old_p = p``, ``p += e_w``, the run-dtype mirror of the moved ``p``) - and
+    ``second_step`` is ``sodt_sam_restore`` followed by the base optimizer's unchanged ``step()``.  Where the reference
+    re-points ``p.data`` at a clone, the restore copies into the flat buffer, so the parameters stay the views the engine
+    checks for.  Nothing on the way reads the device.
+
+    Deviations from the reference: the norm is accumulated in float64 over the flat buffer (the reference: one float32 norm per
+    tensor and a float32 norm of those), and a first gradient that is not finite leaves the weights unperturbed (the
+    reference writes NaN into every weight and restores it afterwards); ``sam_info()`` reports the flag.
+
+    With a ``GradScaler``: ``scaler.scale(loss).backward(); opt.first_step(zero_grad=True, scaler=scaler);
+    scaler.scale(loss2).backward(); scaler.step(opt); scaler.update()`` - the closure-less ``step()`` acts as ``second_step()``
+    when a first step is pending, and the scale / found-inf tensors ``GradScaler.step`` sets go through to the base."""
+
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params, base_optimizer, model, rho: float = 0.05, adaptive: bool = False, **kwargs):
+        if not rho >= 0.0:
+            raise ValueError(f"Invalid rho, should be non-negative: {rho}")
+        if not (isinstance(base_optimizer, type) and issubclass(base_optimizer, _FusedOptimizer)):
+            raise TypeError("FusedSAM: base_optimizer is the class FusedSGD or FusedAdam")
+        super().__init__(params, dict(rho=rho, adaptive=adaptive))
+        self.base_optimizer = base_optimizer(self.param_groups, model, **kwargs)
+        self.param_groups = self.base_optimizer.param_groups
+        self.defaults.update(self.base_optimizer.defaults)
+        self.model = model
+        self._rec = None           # the device record of sodt_sam_norm (ops.new_sam_rec), made at the first first_step
+        self._old = None           # old_p: scratch of the flat parameters' layout, never saved
+        self._pending = None       # (engine, chunk -> group map) of a first_step whose second_step has not run
+
+    def _hyp(self):
+        rho, adaptive = [float(g["rho"]) for g in self.param_groups], [bool(g["adaptive"]) for g in self.param_groups]
+        if not all(r >= 0.0 for r in rho):
+            raise ValueError(f"Invalid rho, should be non-negative: {rho}")
+        return rho, adaptive
+
+    @torch.no_grad()
+    def first_step(self, zero_grad: bool = False, scaler=None):
+        base = self.base_optimizer
+        rho, adaptive = self._hyp()
+        scale = None
+        if scaler is not None and scaler.is_enabled():
+            scale = scaler._scale            # the device tensor; get_scale() would synchronise
+            if scale is None:
+                raise RuntimeError("FusedSAM.first_step: the GradScaler has no scale yet (scaler.scale(loss).backward() comes first)")
+        if self._pending is not None:
+            raise RuntimeError("FusedSAM.first_step: the previous first_step has not been followed by second_step / step")
+        eng = base._bind()
+        eng._check_param_views()
+        if eng._claim_grads():              # no backward since zero_grad(set_to_none=True): nothing to climb along, nothing pending
+            # _FusedOptimizer.step keeps the views it has just claimed and zeroes the buffer under them.  Here the views are handed
+            # back instead, so that the base step that follows also sees that no backward ran and skips (with the views kept it
+            # would step on a zero gradient: decay and momentum would move the weights).  The buffer needs no zeroing then:
+            # nothing reads it before the next backward claims the views afresh, and that backward zeroes it first.
+            for _, p, _, ptr in eng._claim:
+                if p.grad is not None and p.grad.data_ptr() == ptr:
+                    p.grad = None
+            return
+        dev = eng.flat_param.device
+        if self._rec is None or self._rec.device != dev:
+            self._rec = ops.new_sam_rec(dev)
+        if self._old is None or self._old.shape != eng.flat_param.shape or self._old.device != dev:
+            self._old = torch.empty_like(eng.flat_param)
+        cast = next(iter(eng.flat_cast.values())) if eng.flat_cast else None
+        # the perturbation writes the mirror of the chunks it owns only: the mirror is whole afterwards if it was whole before
+        whole = cast is not None and eng.param_cast_fresh and eng._cast_version == eng.params_version()
+        ops.sam_norm(eng.flat_param if any(adaptive) else None, eng.flat_grad, base._groups, adaptive, self._rec, scale)
+        ops.sam_perturb(eng.flat_param, eng.flat_grad, self._old, cast, base._groups, rho, adaptive, self._rec)
+        self._pending = (eng, base._groups)
+        if whole:
+            eng.mark_cast_fresh()
+        else:
+            eng.invalidate_params()
+        if zero_grad:
+            self.zero_grad(set_to_none=True)      # the weight-gradient kernels accumulate: the second backward starts from zero
+
+    @torch.no_grad()
+    def second_step(self, zero_grad: bool = False):
+        base = self.base_optimizer
+        if self._pending is not None:
+            eng, groups = self._pending
+            self._pending = None
+            eng._check_param_views()
+            ops.sam_restore(eng.flat_param, self._old, groups)
+            eng.invalidate_params()         # (the base step rewrites the mirror and marks it fresh; a step without gradients does not)
+        amp = {k: getattr(self, k) for k in ("grad_scale", "found_inf") if hasattr(self, k)}     # set by GradScaler.step
+        for k, v in amp.items():
+            setattr(base, k, v)
+        try:
+            base.step()
+        finally:
+            for k in amp:
+                delattr(base, k)
+        if zero_grad:
+            self.zero_grad(set_to_none=True)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is None:
+            if self._pending is None:
+                raise RuntimeError("Sharpness Aware Minimization requires closure, but it was not provided")
+            self.second_step()
+            return None
+        self.first_step(zero_grad=True)
+        with torch.enable_grad():           # (step() itself runs under no_grad; the closure's forward and backward must not)
+            closure()
+        self.second_step()
+        return None
+
+    def sam_info(self):
+        """``(found, norm)`` of the last ``first_step`` as one-element DEVICE tensors (f32 0 / 1: the gradient was not finite and
+        the weights were left unperturbed; f64 norm of the unscaled gradient, weighted by |p| in adaptive groups), or
+        ``(None, None)`` before the first one.  Copies made on the device; this call forces no synchronisation."""
+        if self._rec is None:
+            return None, None
+        return ops.sam_rec_field(self._rec, "found").clone(), ops.sam_rec_field(self._rec, "norm").clone()
+
+    def last_step_info(self):
+        return self.base_optimizer.last_step_info()
+
+    def state_dict(self):
+        return self.base_optimizer.state_dict()          # (rho / adaptive ride in the shared param_groups; old_p is scratch)
+
+    def load_state_dict(self, sd):
+        self.base_optimizer.load_state_dict(sd)
+        self.param_groups = self.base_optimizer.param_groups
