@@ -261,13 +261,18 @@ def swin_block(sd: SD, pfx: str, x: Tensor, H: int, W: int, window: int, shift: 
     return st(x + mlp(sd, pfx + "mlp.", xn2, H, W, linear_mlp, store), "xo")
 
 
-def patch_merging(sd: SD, pfx: str, x: Tensor, H: int, W: int) -> Tensor:
-    """PatchMerging.forward (backbone_vit.py:839-860)."""
+def patch_merging(sd: SD, pfx: str, x: Tensor, H: int, W: int, store=None) -> Tensor:
+    """PatchMerging.forward (backbone_vit.py:839-860).
+
+    store(t, name) (default: the identity; see swin_block) is applied where a reduced-precision run writes a value to memory: the
+    input "x" (its gradient on the way back), the reduction's output "z", which the LayerNorm reads back, and the LayerNorm's
+    output "y".  The LayerNorm's statistics and parameters stay wide."""
+    st = store if store is not None else _identity
     B, L, C = x.shape
-    x = x.view(B, H, W, C)
+    x = st(x, "x").view(B, H, W, C)
     x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
-    x = x.view(B, -1, 4 * C) @ sd[pfx + "reduction.weight"].t()
-    return layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"])
+    x = st(x.view(B, -1, 4 * C) @ sd[pfx + "reduction.weight"].t(), "z")
+    return st(layer_norm(x, sd[pfx + "norm.weight"], sd[pfx + "norm.bias"]), "y")
 
 
 def image_encoder(sd: SD, x4: Tensor, pfx: str = "image_encoder.", taps: Optional[dict] = None,
@@ -312,44 +317,73 @@ def image_encoder(sd: SD, x4: Tensor, pfx: str = "image_encoder.", taps: Optiona
 # ----------------------------------------------------------------------------
 # head (YOLOv5 blocks, NCHW)
 # ----------------------------------------------------------------------------
-def conv_bn_silu(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict]) -> Tensor:
-    """Conv.forward / fuseforward (common.py:38-52): Conv2d(bias=False)+BN(eps 1e-3,
-    momentum 0.03)+SiLU; k in {1,3}, autopad."""
+def _identity(t: Tensor, name: str) -> Tensor:
+    return t
+
+
+def _conv_bn_silu(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict], st) -> Tensor:
+    """conv_bn_silu behind its input's store point (a C3 / SPP input is stored once, whatever reads it)."""
     w = sd[pfx + "conv.weight"]
     k = w.shape[-1]
     z = F.conv2d(x, w, None, stride=1, padding=k // 2)
     if pfx + "bn.weight" not in sd:                       # fused model (model.py:317-325)
         z = z + sd[pfx + "conv.bias"].view(1, -1, 1, 1)
-        return F.silu(z)
+        return st(F.silu(z), pfx + "y")
     rm, rv = sd[pfx + "bn.running_mean"], sd[pfx + "bn.running_var"]
     if training:
-        mean = z.mean(dim=(0, 2, 3))
+        mean = z.mean(dim=(0, 2, 3))                      # the statistics stay wide: the sums are taken before z is stored
         var = z.var(dim=(0, 2, 3), unbiased=False)
         if new_stats is not None:
             n = z.numel() / z.shape[1]
             new_stats[pfx + "bn.running_mean"] = (1 - BN_MOMENTUM) * rm + BN_MOMENTUM * mean.detach()
             new_stats[pfx + "bn.running_var"] = (1 - BN_MOMENTUM) * rv + BN_MOMENTUM * var.detach() * n / (n - 1)
+        z = st(z, pfx + "z")                              # the pre-BN output is stored, and BN normalises what it reads back
     else:
         mean, var = rm, rv
     zn = (z - mean.view(1, -1, 1, 1)) / torch.sqrt(var.view(1, -1, 1, 1) + BN_EPS)
     zn = zn * sd[pfx + "bn.weight"].view(1, -1, 1, 1) + sd[pfx + "bn.bias"].view(1, -1, 1, 1)
-    return F.silu(zn)
+    return st(F.silu(zn), pfx + "y")
 
 
-def c3(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict]) -> Tensor:
-    """C3.forward with n=1 Bottleneck(shortcut=False) (common.py:114-127, :55-65)."""
-    a = conv_bn_silu(sd, pfx + "cv1.", x, training, new_stats)
-    a = conv_bn_silu(sd, pfx + "m.0.cv1.", a, training, new_stats)
-    a = conv_bn_silu(sd, pfx + "m.0.cv2.", a, training, new_stats)
-    b = conv_bn_silu(sd, pfx + "cv2.", x, training, new_stats)
-    return conv_bn_silu(sd, pfx + "cv3.", torch.cat((a, b), 1), training, new_stats)
+def conv_bn_silu(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict], store=None) -> Tensor:
+    """Conv.forward / fuseforward (common.py:38-52): Conv2d(bias=False)+BN(eps 1e-3,
+    momentum 0.03)+SiLU; k in {1,3}, autopad.
+
+    store(t, name) (default: the identity; see swin_block) is applied to every value a reduced-precision run of the unit writes
+    to memory or feeds to a matrix unit narrowed.  Names carry the convolution's prefix: the unit input pfx + "x" (its gradient
+    on the way back), the pre-BN output pfx + "z" in training mode (it is stored, and BatchNorm normalises the stored value; in
+    eval mode and in the fused model the affine is the GEMM's epilogue and z never exists), the output pfx + "y".  BN
+    parameters and statistics stay wide: the batch statistics are those of z before it is stored (the sums of a GEMM epilogue's
+    wide accumulators), so the stored z that BN normalises is not exactly centred."""
+    st = store if store is not None else _identity
+    return _conv_bn_silu(sd, pfx, st(x, pfx + "x"), training, new_stats, st)
 
 
-def spp(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict]) -> Tensor:
-    """SPP.forward (common.py:129-140): cv1 -> MaxPool2d(5 | 9 | 13, stride 1, same padding) -> cat -> cv2."""
-    a = conv_bn_silu(sd, pfx + "cv1.", x, training, new_stats)
-    pools = [F.max_pool2d(a, k, 1, k // 2) for k in (5, 9, 13)]
-    return conv_bn_silu(sd, pfx + "cv2.", torch.cat([a] + pools, 1), training, new_stats)
+def c3(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict], store=None) -> Tensor:
+    """C3.forward with n=1 Bottleneck(shortcut=False) (common.py:114-127, :55-65).
+
+    store: as in conv_bn_silu.  Store points: the unit input pfx + "x", once (cv1 and cv2 read the same stored tensor and its
+    gradient is written once), and "<conv>.z" / "<conv>.y" of cv1, m.0.cv1, m.0.cv2, cv2, cv3; the outputs of m.0.cv2 and cv2 are
+    the two slices of the concatenation cv3 reads."""
+    st = store if store is not None else _identity
+    x = st(x, pfx + "x")
+    a = _conv_bn_silu(sd, pfx + "cv1.", x, training, new_stats, st)
+    a = _conv_bn_silu(sd, pfx + "m.0.cv1.", a, training, new_stats, st)
+    a = _conv_bn_silu(sd, pfx + "m.0.cv2.", a, training, new_stats, st)
+    b = _conv_bn_silu(sd, pfx + "cv2.", x, training, new_stats, st)
+    return _conv_bn_silu(sd, pfx + "cv3.", torch.cat((a, b), 1), training, new_stats, st)
+
+
+def spp(sd: SD, pfx: str, x: Tensor, training: bool, new_stats: Optional[dict], store=None) -> Tensor:
+    """SPP.forward (common.py:129-140): cv1 -> MaxPool2d(5 | 9 | 13, stride 1, same padding) -> cat -> cv2.
+
+    store: as in conv_bn_silu.  Store points: the unit input pfx + "x", "<conv>.z" / "<conv>.y" of cv1 and cv2, and the three
+    pooled slices of the concatenation, pfx + "m5.y" / "m9.y" / "m13.y" (a maximum of stored values is one of them: the forward
+    value is untouched, the slice's gradient is stored narrowed on the way back)."""
+    st = store if store is not None else _identity
+    a = _conv_bn_silu(sd, pfx + "cv1.", st(x, pfx + "x"), training, new_stats, st)
+    pools = [st(F.max_pool2d(a, k, 1, k // 2), f"{pfx}m{k}.y") for k in (5, 9, 13)]
+    return _conv_bn_silu(sd, pfx + "cv2.", torch.cat([a] + pools, 1), training, new_stats, st)
 
 
 def detect_raw(sd: SD, pfx: str, x: Tensor, na: int = 3) -> Tensor:
@@ -372,27 +406,31 @@ def detect_decode(raw: Tensor, anchor_grid: Tensor, stride: float = DET_STRIDE) 
 
 
 def head(sd: SD, feats: Sequence[Tensor], training: bool, new_stats: Optional[dict] = None,
-         pfx: str = "detect.") -> Tuple[Tensor, List[Tensor]]:
-    """head graph models/model.yaml:65-74 as wired by Model.forward_once (model.py:268-281)."""
+         pfx: str = "detect.", store=None) -> Tuple[Tensor, List[Tensor]]:
+    """head graph models/model.yaml:65-74 as wired by Model.forward_once (model.py:268-281).  store: see head_graph."""
     y = list(feats)                                              # y[0..2]
-    y.append(conv_bn_silu(sd, pfx + "0.", y[2], training, new_stats))          # y3
+    y.append(conv_bn_silu(sd, pfx + "0.", y[2], training, new_stats, store))   # y3
     y.append(F.interpolate(y[3], scale_factor=2, mode="nearest"))              # y4
     y.append(torch.cat((y[4], y[1]), 1))                                       # y5
-    y.append(c3(sd, pfx + "3.", y[5], training, new_stats))                    # y6
-    y.append(conv_bn_silu(sd, pfx + "4.", y[6], training, new_stats))          # y7
+    y.append(c3(sd, pfx + "3.", y[5], training, new_stats, store))             # y6
+    y.append(conv_bn_silu(sd, pfx + "4.", y[6], training, new_stats, store))   # y7
     y.append(F.interpolate(y[7], scale_factor=2, mode="nearest"))              # y8
     y.append(torch.cat((y[8], y[0]), 1))                                       # y9
-    y.append(c3(sd, pfx + "7.", y[9], training, new_stats))                    # y10
+    y.append(c3(sd, pfx + "7.", y[9], training, new_stats, store))             # y10
     raw = detect_raw(sd, pfx + "8.", y[10])
     return raw, y
 
 
 def head_graph(sd: SD, feats: Sequence[Tensor], rows, training: bool, new_stats: Optional[dict] = None,
-               pfx: str = "detect.") -> Tuple[Tensor, List[Tensor]]:
+               pfx: str = "detect.", store=None) -> Tuple[Tensor, List[Tensor]]:
     """Any head yaml (rows of [from, number, module, args], models/model.yaml:65-74) run as Model.forward_once runs the
     nn.Sequential parse_model built from it (model.py:268-281): the input of row i is y[f] (f = -1: the previous row), or
     the list of them; y[0..2] are the encoder outputs and row i appends y[3 + i].  Modules: Conv, C3, SPP, nn.Upsample,
-    Concat, Detect (common.py:38-140,275-282; model.py:48-55)."""
+    Concat, Detect (common.py:38-140,275-282; model.py:48-55).
+
+    store: handed to every Conv / C3 / SPP row (conv_bn_silu, c3, spp: names carry the row's prefix, "detect.3.cv1.z").  Upsample
+    and Concat rows store nothing: the gradient of a unit's concatenated input is stored once at the unit's "x", and the sum over
+    the children of an up-sampled part is stored at the producing row's "y"."""
     y = list(feats)
     x = None
     raw = None
@@ -403,11 +441,11 @@ def head_graph(sd: SD, feats: Sequence[Tensor], rows, training: bool, new_stats:
             xin = [x if j == -1 else y[j] for j in f]
         p = f"{pfx}{i}."
         if m == "Conv":
-            x = conv_bn_silu(sd, p, xin, training, new_stats)
+            x = conv_bn_silu(sd, p, xin, training, new_stats, store)
         elif m == "C3":
-            x = c3(sd, p, xin, training, new_stats)
+            x = c3(sd, p, xin, training, new_stats, store)
         elif m == "SPP":
-            x = spp(sd, p, xin, training, new_stats)
+            x = spp(sd, p, xin, training, new_stats, store)
         elif m == "nn.Upsample":
             x = F.interpolate(xin, scale_factor=2, mode="nearest")
         elif m == "Concat":

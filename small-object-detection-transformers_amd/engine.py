@@ -1486,33 +1486,14 @@ class Engine:
         if lo < hi:
             plan.bwd_marks.append((ops.recorded_count(), lo, hi))
 
-    def _backward_main(self, plan: Plan, P):
+    def _head_bwd(self, plan: Plan, P, gout, extra):
+        """The head units in reverse, the counterpart of _head_fwd.  gout: headgraph.Ref -> (buffer, ld, column offset) of the
+        gradient at the last unit's output; returns it holding d(f0), d(f1), d(f2) under Ref("enc", j)."""
         B, th, tw = plan.B, plan.H // 4, plan.W // 4
-        wT, g, b = P["wT"], self.g, plan.bufs
-        enc = self.model.image_encoder
-        U, T = plan.unit, plan.trainable
-        ops.zero_(plan.zpool("b"))                   # BN-backward reduction accumulators of every head conv
-        T1, T2, T3 = B * th * tw, B * (th // 2) * (tw // 2), B * (th // 4) * (tw // 4)
-        # ---- Detect
-        hu = self.head.by_row[self.head.head_out[0]]
-        cd = self.head.head_out[1]
-        gout = {}                                                    # headgraph.Ref -> (buffer, ld, column offset)
-        if U("detect").runs_bwd and plan.det_fused:
-            if U("detect").any_dx:                                   # written by the live sodt_detect_bwd (_backward, step (1))
-                gout[hu.ref] = (b["g.dyd"], cd, 0)
-        elif U("detect").runs_bwd:
-            dzd = b["g.dzd"]
-            if U("detect").any_wgrad:
-                ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np,
-                            lddw=cd, dbias=g[self.det_name + "m.0.bias"])
-            if U("detect").any_dx:
-                dyd = plan.buf("g.dyd", (T1, cd))
-                ops.gemm_nt([SegSpec(dzd)], wT[self.det_name + "m.0.weight"], dyd, T1, cd, self.det_np)
-                gout[hu.ref] = (dyd, cd, 0)
+        wT, U = P["wT"], plan.unit
         # ---- head units in reverse: every unit returns d(its concatenated input) [M][c1]; the gradient of an Upsample /
         #      Concat input is a column slice of it (nearest x2^shr upsample: summed over the 2^shr x 2^shr children).  A unit
         #      whose output needs no gradient is passed over; an input that needs none gets no slice (and no gather_sum_rows)
-        extra = self._sr_extra(plan) if self.sr and U("model_up").runs_bwd and U("model_up").any_dx else {}
         for u in reversed(self.head.units):
             H, W = th >> u.level, tw >> u.level
             M = B * H * W
@@ -1552,6 +1533,34 @@ class Engine:
         for j in range(3):
             if Ref("enc", j) in gout:
                 self._add_extra(plan, extra, Ref("enc", j), gout[Ref("enc", j)])
+        return gout
+
+    def _backward_main(self, plan: Plan, P):
+        B, th, tw = plan.B, plan.H // 4, plan.W // 4
+        wT, g, b = P["wT"], self.g, plan.bufs
+        enc = self.model.image_encoder
+        U, T = plan.unit, plan.trainable
+        ops.zero_(plan.zpool("b"))                   # BN-backward reduction accumulators of every head conv
+        T1, T2, T3 = B * th * tw, B * (th // 2) * (tw // 2), B * (th // 4) * (tw // 4)
+        # ---- Detect
+        hu = self.head.by_row[self.head.head_out[0]]
+        cd = self.head.head_out[1]
+        gout = {}                                                    # headgraph.Ref -> (buffer, ld, column offset)
+        if U("detect").runs_bwd and plan.det_fused:
+            if U("detect").any_dx:                                   # written by the live sodt_detect_bwd (_backward, step (1))
+                gout[hu.ref] = (b["g.dyd"], cd, 0)
+        elif U("detect").runs_bwd:
+            dzd = b["g.dzd"]
+            if U("detect").any_wgrad:
+                ops.gemm_tn(dzd, [SegSpec(b[hu.out_name])], g[self.det_name + "m.0.weight"], T1, self.na * self.no, cd, ldy=self.det_np,
+                            lddw=cd, dbias=g[self.det_name + "m.0.bias"])
+            if U("detect").any_dx:
+                dyd = plan.buf("g.dyd", (T1, cd))
+                ops.gemm_nt([SegSpec(dzd)], wT[self.det_name + "m.0.weight"], dyd, T1, cd, self.det_np)
+                gout[hu.ref] = (dyd, cd, 0)
+        # ---- head units in reverse (the SR branch's input gradients join at their taps)
+        extra = self._sr_extra(plan) if self.sr and U("model_up").runs_bwd and U("model_up").any_dx else {}
+        gout = self._head_bwd(plan, P, gout, extra)
         (gf0, ld0, off0), (gf1, ld1, off1), (gf2, ld2, off2) = (gout.get(Ref("enc", j), (None, 0, 0)) for j in range(3))
         # where the head's backward ends and the encoder's begins, and the buffers the head left d(f0), d(f1), d(f2) in
         # (token-major rows, `ld` columns, the feature's columns at `off`): replay_encoder_backward re-runs the rest from there
