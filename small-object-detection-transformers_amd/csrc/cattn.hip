@@ -80,6 +80,14 @@ __global__ __launch_bounds__(256) void patch_embed4_bwd_kernel(const float* __re
 
 __device__ __forceinline__ int pair_kv(int q) { return q == 0 ? 1 : (q == 1 ? 2 : (q == 2 ? 3 : 1)); }   // :508-521
 
+// mean of a LayerNorm row from its sum, as a rounded f32 of its own: contracted into the subtraction that follows, a row of
+// 48 equal values does not centre to exact zeros (see csrc/frontend.hip)
+__device__ __forceinline__ float row_mean(float sum) {
+  float m = sum * (1.0f / CE);
+  asm volatile("" : "+v"(m));   // (the build's -ffp-contract=fast fuses across statements and past a contract pragma)
+  return m;
+}
+
 // window geometry of token (b, y, x) under roll(-shift): window origin in shifted coordinates + mask region id
 __device__ __forceinline__ void ca_window(const CaGeo& g, int y, int x, int& ys0, int& xs0, int& rid) {
   int ys = y - g.shift, xs = x - g.shift;               // shifted[ys] = x[(ys + shift) % H]
@@ -143,7 +151,7 @@ __global__ __launch_bounds__(128) void cross_attn_ln_fwd_kernel(const float* __r
   float mean = 0.f;
 #pragma unroll
   for (int j = 0; j < CE; ++j) mean += s[j];
-  mean *= (1.0f / CE);
+  mean = row_mean(mean);
   float var = 0.f;
 #pragma unroll
   for (int j = 0; j < CE; ++j) { const float d = s[j] - mean; var += d * d; }

@@ -54,6 +54,15 @@ __device__ __forceinline__ void load_patch(const float* __restrict__ rgb, const 
   }
 }
 
+// mean of a LayerNorm row from its sum, as a rounded f32 of its own.  Contracted into the subtraction that follows
+// (s - sum * (1/48) as one FMA) a row of 48 equal values does not centre to exact zeros: the residue s * 2^-25 meets
+// rstd = 1/sqrt(1e-5) there and the output is off beta by 1e-4 |s|.
+__device__ __forceinline__ float row_mean(float sum) {
+  float m = sum * (1.0f / CE);
+  asm volatile("" : "+v"(m));   // (the build's -ffp-contract=fast fuses across statements and past a contract pragma)
+  return m;
+}
+
 // pair q: query plane / key-value plane  (backbone_vit.py:508-521)
 __device__ __forceinline__ int pair_q(int q) { return q; }
 __device__ __forceinline__ int pair_kv(int q) { return q == 0 ? 1 : (q == 1 ? 2 : (q == 2 ? 3 : 1)); }
@@ -112,7 +121,7 @@ __global__ __launch_bounds__(256) void frontend_fwd_kernel(const float* __restri
   float mean = 0.f;
 #pragma unroll
   for (int j = 0; j < CE; ++j) { s[j] = sE[qa][lane][j] + sE[qb][lane][j]; mean += s[j]; }
-  mean *= (1.0f / CE);
+  mean = row_mean(mean);
   float var = 0.f;
 #pragma unroll
   for (int j = 0; j < CE; ++j) { const float d = s[j] - mean; var += d * d; }
