@@ -481,44 +481,120 @@ def model_forward(sd: SD, x_rgb: Tensor, x_ir: Tensor, training: bool = True,
 # ----------------------------------------------------------------------------
 # super-resolution auxiliary branch (DeepLab = Decoder + EDSR x8), used in training with --super
 # ----------------------------------------------------------------------------
-def sr_decoder(sd: SD, pfx: str, x: Tensor, low: Tensor, factor: int = 2) -> Tensor:
-    """Decoder.forward (basics/models/sr_decoder_noBN_noD.py:27-45): 1x1 convs (no bias) + ReLU on both inputs, bilinear
-    (align_corners=True) resize of both to low's size x (factor // 2), concat (x first), 3x3 - ReLU - 3x3 - ReLU - 1x1(+bias)."""
-    lo = F.relu(F.conv2d(low, sd[pfx + "conv1.weight"]))
-    xx = F.relu(F.conv2d(x, sd[pfx + "conv2.weight"]))
+def sr_decoder_entry(sd: SD, pfx: str, x: Tensor, low: Tensor, factor: int = 2, store=None) -> Tensor:
+    """The Decoder up to its concatenation: 1x1 (no bias) + ReLU on both inputs, the bilinear (align_corners=True) resize of both
+    to low's size x (factor // 2), concat (x first).  Store points: see sr_decoder."""
+    st = store if store is not None else _identity
+    lo = st(F.relu(F.conv2d(st(low, pfx + "low"), sd[pfx + "conv1.weight"])), pfx + "a")
+    xx = st(F.relu(F.conv2d(st(x, pfx + "x"), sd[pfx + "conv2.weight"])), pfx + "xr")
     size = [d * (factor // 2) for d in lo.shape[2:]]
-    xx = F.interpolate(xx, size=size, mode="bilinear", align_corners=True)
+    xx = st(F.interpolate(xx, size=size, mode="bilinear", align_corners=True), pfx + "cat.x")
     if factor > 1:
-        lo = F.interpolate(lo, size=size, mode="bilinear", align_corners=True)
-    z = torch.cat((xx, lo), 1)
-    z = F.relu(F.conv2d(z, sd[pfx + "last_conv.0.weight"], None, padding=1))
-    z = F.relu(F.conv2d(z, sd[pfx + "last_conv.2.weight"], None, padding=1))
-    return F.conv2d(z, sd[pfx + "last_conv.4.weight"], sd[pfx + "last_conv.4.bias"])
+        lo = F.interpolate(lo, size=size, mode="bilinear", align_corners=True)      # (factor 2: the identity, nothing is written)
+    return torch.cat((xx, lo), 1)
 
 
-def edsr(sd: SD, pfx: str, x: Tensor) -> Tensor:
+def sr_decoder_tail(sd: SD, pfx: str, z: Tensor, store=None) -> Tensor:
+    """The Decoder's last_conv on the concatenation: 3x3 - ReLU - 3x3 - ReLU - 1x1(+bias).  Store points: see sr_decoder."""
+    st = store if store is not None else _identity
+    z = st(F.relu(F.conv2d(z, sd[pfx + "last_conv.0.weight"], None, padding=1)), pfx + "d1")
+    z = st(F.relu(F.conv2d(z, sd[pfx + "last_conv.2.weight"], None, padding=1)), pfx + "d2")
+    return st(F.conv2d(z, sd[pfx + "last_conv.4.weight"], sd[pfx + "last_conv.4.bias"]), pfx + "d3")
+
+
+def sr_decoder(sd: SD, pfx: str, x: Tensor, low: Tensor, factor: int = 2, store=None) -> Tensor:
+    """Decoder.forward (basics/models/sr_decoder_noBN_noD.py:27-45): 1x1 convs (no bias) + ReLU on both inputs, bilinear
+    (align_corners=True) resize of both to low's size x (factor // 2), concat (x first), 3x3 - ReLU - 3x3 - ReLU - 1x1(+bias).
+
+    store(t, name) (default: the identity; see swin_block) is applied to every value a reduced-precision run writes to memory;
+    the gradient of a stored value is stored at the same point on the way back.  Store points, by the buffer names of sr.py
+    (SRBranch.decoder_forward / decoder_backward): the inputs pfx + "low" / "x" (gradients g.low / g.x); "a", the low-level
+    slice of the concatenation after its ReLU (g.a, masked); "xr", the deep 1x1 after its ReLU, on its own grid (g.xr,
+    masked); "cat.x", the resized slice (g.cu); "d1" / "d2" after their ReLU (g.d1 / g.d2, masked); "d3".  Every launch adds
+    bias / ReLU to its wide accumulator and rounds once."""
+    return sr_decoder_tail(sd, pfx, sr_decoder_entry(sd, pfx, x, low, factor, store), store)
+
+
+def _sr_conv3(sd: SD, name: str, t: Tensor) -> Tensor:
+    return F.conv2d(t, sd[name + ".weight"], sd[name + ".bias"], padding=1)
+
+
+def edsr_head(sd: SD, pfx: str, x: Tensor, store=None) -> Tensor:
+    """The head 3x3 (edsr.py:60-61).  Stored: the input "x" and the output "h"."""
+    st = store if store is not None else _identity
+    return st(_sr_conv3(sd, pfx + "head.0", st(x, pfx + "x")), pfx + "h")
+
+
+def edsr_resblock(sd: SD, pfx: str, i: int, r: Tensor, store=None) -> Tensor:
+    """ResBlock i (edsr.py:34-53): r + conv(ReLU(conv(r))).  Stored: "body.<i>.u" after the ReLU (g.u, masked) and "body.<i>.r",
+    the sum (the residual is added to the wide accumulator: one rounding; on the way back g.r* = conv^T(g.u) + g.r, one rounding)."""
+    st = store if store is not None else _identity
+    u = st(F.relu(_sr_conv3(sd, f"{pfx}body.{i}.body.0", r)), f"{pfx}body.{i}.u")
+    return st(r + _sr_conv3(sd, f"{pfx}body.{i}.body.2", u), f"{pfx}body.{i}.r")
+
+
+def edsr_body_close(sd: SD, pfx: str, depth: int, r: Tensor, h: Tensor, store=None) -> Tensor:
+    """The body's closing 3x3 + the head output (edsr.py:93-94).  Stored: "rb", the sum (one rounding)."""
+    st = store if store is not None else _identity
+    return st(_sr_conv3(sd, f"{pfx}body.{depth}", r) + h, pfx + "rb")
+
+
+def edsr_upsampler_stage(sd: SD, pfx: str, j: int, r: Tensor, store=None) -> Tensor:
+    """Upsampler stage j (edsr.py:14-24): 3x3 to 4 n_feat channels + PixelShuffle(2).  Stored: "p<j>", the shuffled output.  A
+    reduced-precision run computes the stage as four 64 -> 64 convolutions, plane p = 2 i + j being the output channels 4 c + p;
+    on the way back launch p adds its input gradient to what the launches before it stored, so the stage's input gradient is a
+    running narrow sum: "tail.0.<2j>.acc<p>" (p = 1, 2, 3) are the three extra stores (the value is the stage's input, unchanged);
+    the fourth is the store of the input itself.  Without a store the stage is the one convolution it always was."""
+    name = f"{pfx}tail.0.{2 * j}"
+    if store is None:
+        return F.pixel_shuffle(_sr_conv3(sd, name, r), 2)
+    w, b = sd[name + ".weight"], sd[name + ".bias"]
+    planes, t = [None] * 4, r
+    for p in (3, 2, 1, 0):                                   # plane 0's gradient is stored first, plane 3's added last
+        planes[p] = F.conv2d(t, w[p::4], b[p::4], padding=1)
+        if p:
+            t = store(t, f"{name}.acc{p}")
+    z = torch.stack(planes, 2).flatten(1, 2)                 # channel 4 c + p
+    return store(F.pixel_shuffle(z, 2), f"{pfx}p{j}")
+
+
+def edsr_close(sd: SD, pfx: str, r: Tensor, store=None) -> Tensor:
+    """The closing 3x3 to num_channels (edsr.py:81-84).  Store point "y": the float32 result.  A run that writes the float32
+    output itself stores it unrounded and reads the float32 gradient narrowed (sr.py: the y_nchw / dy_nchw forms, at most 4
+    channels); one that goes through rows of the run dtype rounds both ways - the caller's store tells them apart by the name."""
+    st = store if store is not None else _identity
+    return st(_sr_conv3(sd, pfx + "tail.1", r), pfx + "y")
+
+
+def edsr(sd: SD, pfx: str, x: Tensor, store=None) -> Tensor:
     """EDSR.forward (basics/models/edsr.py:55-102): head 3x3; ResBlocks (3x3 - ReLU - 3x3, + input; res_scale 1) and a closing 3x3,
     + head output; tail: log2(scale) x (3x3 to 4 n_feat channels + PixelShuffle(2)), 3x3 to num_channels.  Depth / scale are read
-    off the state dict (body.<i>.body.0 / tail.0.<2j>)."""
-    def conv(name, t):
-        return F.conv2d(t, sd[pfx + name + ".weight"], sd[pfx + name + ".bias"], padding=1)
-    h = conv("head.0", x)
-    r = h
+    off the state dict (body.<i>.body.0 / tail.0.<2j>).
+
+    store: as in sr_decoder.  Store points, by the buffer names of sr.py (SRBranch.edsr_forward / edsr_backward): the input
+    pfx + "x" (gradient g.ein); "h", the head output (its gradient is the sum add_rows(dr, d_rb) writes); "body.in", the same
+    value as the first ResBlock reads it (forward unchanged; its gradient is the chain's g.r*, stored before that sum);
+    "body.<i>.u" / "body.<i>.r" (g.u / g.r*); "rb" (g.p0); "tail.0.<2j>.acc<p>" and "p<j>" of each Upsampler stage
+    (edsr_upsampler_stage; g.p<j + 1>); "y" (edsr_close)."""
+    st = store if store is not None else _identity
+    h = edsr_head(sd, pfx, x, store)
+    r = st(h, pfx + "body.in")
     i = 0
     while f"{pfx}body.{i}.body.0.weight" in sd:
-        r = r + conv(f"body.{i}.body.2", F.relu(conv(f"body.{i}.body.0", r)))
+        r = edsr_resblock(sd, pfx, i, r, store)
         i += 1
-    r = conv(f"body.{i}", r) + h
+    r = edsr_body_close(sd, pfx, i, r, h, store)
     j = 0
-    while f"{pfx}tail.0.{j}.weight" in sd:
-        r = F.pixel_shuffle(conv(f"tail.0.{j}", r), 2)
-        j += 2
-    return conv("tail.1", r)
+    while f"{pfx}tail.0.{2 * j}.weight" in sd:
+        r = edsr_upsampler_stage(sd, pfx, j, r, store)
+        j += 1
+    return edsr_close(sd, pfx, r, store)
 
 
-def deeplab_sr(sd: SD, pfx: str, low: Tensor, x: Tensor, factor: int = 2) -> Tensor:
-    """DeepLab.forward (basics/models/deeplabedsr.py:61-73): EDSR(sr_decoder(x, low_level_feat, factor))."""
-    return edsr(sd, pfx + "edsr.", sr_decoder(sd, pfx + "sr_decoder.", x, low, factor))
+def deeplab_sr(sd: SD, pfx: str, low: Tensor, x: Tensor, factor: int = 2, store=None) -> Tensor:
+    """DeepLab.forward (basics/models/deeplabedsr.py:61-73): EDSR(sr_decoder(x, low_level_feat, factor)).  store: the store
+    points of sr_decoder and edsr (the Decoder's "d3" is EDSR's "x": stored once)."""
+    return edsr(sd, pfx + "edsr.", sr_decoder(sd, pfx + "sr_decoder.", x, low, factor, store), store)
 
 
 # ----------------------------------------------------------------------------

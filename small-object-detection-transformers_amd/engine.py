@@ -1311,10 +1311,17 @@ class Engine:
             if getattr(br, "_prep_version", None) != ver:
                 br.prepare()
                 br._prep_version = ver
+        low, deep = self._sr_segs(plan)
+        return br.forward(low, deep, B, t, t)
+
+    def _sr_segs(self, plan: Plan):
+        """The branch's two inputs (low-level on the stride-4 grid, deep on the stride-8 grid) as K-segment views of the tapped
+        features' buffers."""
+        t = plan.H // 4
         def segs(parts, level):
             h = t >> level
             return [SegSpec(self._ref_buf(plan, ref), c, 0, 0, 0, 1, shr, h >> shr, h >> shr) for ref, c, shr in parts]
-        return br.forward(segs(self.head.sr_parts[0], 0), segs(self.head.sr_parts[1], 1), B, t, t)
+        return segs(self.head.sr_parts[0], 0), segs(self.head.sr_parts[1], 1)
 
     def _sr_backward(self, plan: Plan, dsr):
         """SR gradients: parameters into the flat buffer, inputs into plan.sr's dense buffers (zero when the SR output took no part

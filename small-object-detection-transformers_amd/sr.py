@@ -149,6 +149,7 @@ class SRBranch:
         # need_dx False: the branch's two inputs need no gradient, the two entry convolutions compute none
         self.trainable = lambda *names: True
         self.need_dx = True
+        self.f_rb, self.f_t = {}, {}             # what the ResBlocks / Upsampler stages keep for their backward, by index
         self.prepare()
 
     def prepare(self):
@@ -264,9 +265,9 @@ class SRBranch:
                     aux_off=aux_off, resid=resid)
 
     # ------------------------------------------------------------------ Decoder (sr_decoder_noBN_noD.py:27-45)
-    def decoder_forward(self, low_parts: Sequence[SegSpec], x_parts: Sequence[SegSpec], B: int, H: int, W: int) -> torch.Tensor:
-        """low_parts: the low-level feature (c1 channels on the H x W grid) as K-segments (upsampling views allowed: set shr / Hi / Wi);
-        x_parts: the deep feature (c2 channels on the H/2 x W/2 grid).  Returns the [B*H*W][64] buffer."""
+    # decoder_forward / decoder_backward are these units in sequence; tests/test_sr_routes_gpu.py runs each one alone.
+    def _dec_entry_fwd(self, low_parts: Sequence[SegSpec], x_parts: Sequence[SegSpec], B: int, H: int, W: int) -> torch.Tensor:
+        """The two 1x1 + ReLU and the resize -> cat [B*H*W][cx + ca] = [x resized | low]."""
         assert H % 2 == 0 and W % 2 == 0
         d, c = self.dec, self.c
         h, w = H // 2, W // 2
@@ -280,6 +281,13 @@ class SRBranch:
         xr = self._buf("xr", (Mh, cx))
         self.f_c2 = self._conv(d + "conv2", x_parts, h, w, Mh, xr, relu=True)
         ops.bilinear_up2_fwd(xr, cat, B, h, w, cx, ldy=cx + ca, ycol=0)
+        return cat
+
+    def _dec_tail_fwd(self, cat: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """last_conv: 3x3 + ReLU -> 3x3 + ReLU -> 1x1 + bias on the concatenation -> d3 [B*H*W][64]."""
+        d = self.dec
+        M1 = B * H * W
+        self.geo = (B, H, W)
         d1 = self._buf("d1", (M1, 256))
         self.f_l0 = self._conv(d + "last_conv.0", [SegSpec(cat)], H, W, M1, d1, relu=True)
         d2 = self._buf("d2", (M1, 128))
@@ -288,13 +296,16 @@ class SRBranch:
         self.f_l4 = self._conv(d + "last_conv.4", [SegSpec(d2)], H, W, M1, d3)
         return d3
 
-    def decoder_backward(self, d3g: torch.Tensor):
-        """d3g [B*H*W][64].  Returns (d_low [B*H*W][c1], d_x [B*(H/2)*(W/2)][c2]): the gradients of the two inputs on their own
-        grids, dense (the gradient of an upsampling / concatenating input view is reduced / split by the caller)."""
+    def decoder_forward(self, low_parts: Sequence[SegSpec], x_parts: Sequence[SegSpec], B: int, H: int, W: int) -> torch.Tensor:
+        """low_parts: the low-level feature (c1 channels on the H x W grid) as K-segments (upsampling views allowed: set shr / Hi / Wi);
+        x_parts: the deep feature (c2 channels on the H/2 x W/2 grid).  Returns the [B*H*W][64] buffer."""
+        return self._dec_tail_fwd(self._dec_entry_fwd(low_parts, x_parts, B, H, W), B, H, W)
+
+    def _dec_tail_bwd(self, d3g: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """d3g [B*H*W][64] -> (g.cu, g.a): the gradient of the concatenation's two slices, the low-level one behind its ReLU mask."""
         B, H, W = self.geo
         d, c, b = self.dec, self.c, self.bufs
-        h, w = H // 2, W // 2
-        M1, Mh = B * H * W, B * h * w
+        M1 = B * H * W
         ca, cx = c[d + "conv1"].cout, c[d + "conv2"].cout
         d2g = self._buf("g.d2", (M1, 128))
         self._conv_bwd(d + "last_conv.4", d3g, 64, self.f_l4, H, W, M1, d2g, drelu_aux=b["d2"])
@@ -305,6 +316,15 @@ class SRBranch:
         self._conv_bwd(d + "last_conv.0", d1g, 256, self.f_l0, H, W, M1, dcu, dx_n=cx, w_row0=0)
         self._conv_bwd(d + "last_conv.0", d1g, 256, self.f_l0, H, W, M1, da, dx_n=ca, w_row0=cx, drelu_aux=b["cat"], aux_off=cx,
                        wgrad=False)
+        return dcu, da
+
+    def _dec_entry_bwd(self, dcu: torch.Tensor, da: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(g.cu, g.a) -> (d_low, d_x) through the resize (+ conv2's ReLU mask) and the two 1x1."""
+        B, H, W = self.geo
+        d, c, b = self.dec, self.c, self.bufs
+        h, w = H // 2, W // 2
+        M1, Mh = B * H * W, B * h * w
+        ca, cx = c[d + "conv1"].cout, c[d + "conv2"].cout
         dxr = self._buf("g.xr", (Mh, cx))
         ops.bilinear_up2_bwd(dcu, dxr, B, h, w, cx, relu_out=b["xr"])
         d_low = self._buf("g.low", (M1, c[d + "conv1"].cin))
@@ -313,45 +333,56 @@ class SRBranch:
         self._conv_bwd(d + "conv2", dxr, cx, self.f_c2, h, w, Mh, d_x if self.need_dx else None)
         return d_low, d_x
 
+    def decoder_backward(self, d3g: torch.Tensor):
+        """d3g [B*H*W][64].  Returns (d_low [B*H*W][c1], d_x [B*(H/2)*(W/2)][c2]): the gradients of the two inputs on their own
+        grids, dense (the gradient of an upsampling / concatenating input view is reduced / split by the caller)."""
+        return self._dec_entry_bwd(*self._dec_tail_bwd(d3g))
+
     # ------------------------------------------------------------------ EDSR (edsr.py:55-102)
-    def edsr_forward(self, x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
-        """x [B*H*W][64] -> (B, ch, 8H, 8W) float32."""
-        e, c = self.ed, self.c
-        M1 = B * H * W
-        self.egeo = (B, H, W)
-        hd = self._buf("e.h", (M1, 64))
-        self.f_h = self._conv(e + "head.0", [SegSpec(x)], H, W, M1, hd)
-        r = hd
-        self.f_rb = []
-        for i in range(self.depth):
-            u = self._buf(f"e.u{i}", (M1, 64))
-            f0 = self._conv(f"{e}body.{i}.body.0", [SegSpec(r)], H, W, M1, u, relu=True)
-            rn = self._buf(f"e.r{i}", (M1, 64))
-            f2 = self._conv(f"{e}body.{i}.body.2", [SegSpec(u)], H, W, M1, rn, resid=r)
-            self.f_rb.append((f0, f2, u))
-            r = rn
-        rb = self._buf("e.rb", (M1, 64))
-        self.f_b = self._conv(f"{e}body.{self.depth}", [SegSpec(r)], H, W, M1, rb, resid=hd)
-        cur, gh, gw = rb, H, W
-        self.f_t = []
-        j = 0
-        while f"{e}tail.0.{2 * j}" in c:
-            cj = c[f"{e}tail.0.{2 * j}"]
-            pj = self._buf(f"e.p{j}", (B * 4 * gh * gw, 64))
-            if cj.wTp is not None:
-                # conv(64 -> 256) + PixelShuffle(2): plane p = 2 i + j (output channels 4 c + p) is a 64 -> 64 convolution whose pixel
-                # (y, x) is stored at (2 y + i, 2 x + j) of the shuffled tensor - no 256-channel tensor, no shuffle launch
-                for pl in range(4):
-                    ops.conv3_c64_fwd(cur, cj.w, pj, B, gh, gw, bias=cj.bias, geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
-                fj = ("direct", cur)
-            else:
-                z = self._buf(f"e.z{j}", (B * gh * gw, 256))
-                fj = self._conv(f"{e}tail.0.{2 * j}", [SegSpec(cur)], gh, gw, B * gh * gw, z)
-                ops.pixel_shuffle2(z, pj, B, gh, gw, 64)
-            self.f_t.append((fj, gh, gw))
-            cur, gh, gw = pj, 2 * gh, 2 * gw
-            j += 1
-        ct = c[e + "tail.1"]
+    # edsr_forward / edsr_backward are these units in sequence; tests/test_sr_routes_gpu.py runs each one alone.
+    def _head_fwd(self, x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        hd = self._buf("e.h", (B * H * W, 64))
+        self.f_h = self._conv(self.ed + "head.0", [SegSpec(x)], H, W, B * H * W, hd)
+        return hd
+
+    def _resblock_fwd(self, i: int, r: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """ResBlock i: r + conv(ReLU(conv(r)))"""
+        e, M1 = self.ed, B * H * W
+        u = self._buf(f"e.u{i}", (M1, 64))
+        f0 = self._conv(f"{e}body.{i}.body.0", [SegSpec(r)], H, W, M1, u, relu=True)
+        rn = self._buf(f"e.r{i}", (M1, 64))
+        f2 = self._conv(f"{e}body.{i}.body.2", [SegSpec(u)], H, W, M1, rn, resid=r)
+        self.f_rb[i] = (f0, f2, u)
+        return rn
+
+    def _body_close_fwd(self, r: torch.Tensor, hd: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """the body's closing convolution + the head output"""
+        rb = self._buf("e.rb", (B * H * W, 64))
+        self.f_b = self._conv(f"{self.ed}body.{self.depth}", [SegSpec(r)], H, W, B * H * W, rb, resid=hd)
+        return rb
+
+    def _up_fwd(self, j: int, cur: torch.Tensor, B: int, gh: int, gw: int) -> torch.Tensor:
+        """Upsampler stage j on the gh x gw grid: conv(64 -> 256) + PixelShuffle(2) -> [B*2gh*2gw][64]"""
+        e = self.ed
+        cj = self.c[f"{e}tail.0.{2 * j}"]
+        pj = self._buf(f"e.p{j}", (B * 4 * gh * gw, 64))
+        if cj.wTp is not None:
+            # conv(64 -> 256) + PixelShuffle(2): plane p = 2 i + j (output channels 4 c + p) is a 64 -> 64 convolution whose pixel
+            # (y, x) is stored at (2 y + i, 2 x + j) of the shuffled tensor - no 256-channel tensor, no shuffle launch
+            for pl in range(4):
+                ops.conv3_c64_fwd(cur, cj.w, pj, B, gh, gw, bias=cj.bias, geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
+            fj = ("direct", cur)
+        else:
+            z = self._buf(f"e.z{j}", (B * gh * gw, 256))
+            fj = self._conv(f"{e}tail.0.{2 * j}", [SegSpec(cur)], gh, gw, B * gh * gw, z)
+            ops.pixel_shuffle2(z, pj, B, gh, gw, 64)
+        self.f_t[j] = (fj, gh, gw)
+        return pj
+
+    def _close_fwd(self, cur: torch.Tensor, B: int, gh: int, gw: int) -> torch.Tensor:
+        """the closing 64 -> ch convolution on the gh x gw grid -> (B, ch, gh, gw) float32"""
+        e = self.ed
+        ct = self.c[e + "tail.1"]
         y = torch.empty(B, ct.cout, gh, gw, device=self.dev, dtype=torch.float32)
         if ops.conv3_n8_ok(cur, ct.cin, ct.np_, ct.k) and ct.cout <= 4 and cur.shape[-1] == 64:
             # the closing convolution writes the (B, ch, 8H, 8W) float32 output itself (no [M][8] rows, no conversion launch)
@@ -363,14 +394,25 @@ class SRBranch:
             ops.nchw_f32_from_rows(o, y, B, ct.cout, gh, gw)
         return y
 
-    def edsr_backward(self, dy: torch.Tensor) -> torch.Tensor:
-        """dy (B, ch, 8H, 8W) float32 -> d(input) [B*H*W][64]."""
-        B, H, W = self.egeo
-        e, c = self.ed, self.c
-        M1 = B * H * W
-        nt = len(self.f_t)
-        gh, gw = H << nt, W << nt
-        ct = c[e + "tail.1"]
+    def edsr_forward(self, x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """x [B*H*W][64] -> (B, ch, 8H, 8W) float32."""
+        self.egeo = (B, H, W)
+        self.f_rb, self.f_t = {}, {}
+        hd = self._head_fwd(x, B, H, W)
+        r = hd
+        for i in range(self.depth):
+            r = self._resblock_fwd(i, r, B, H, W)
+        cur, gh, gw = self._body_close_fwd(r, hd, B, H, W), H, W
+        j = 0
+        while f"{self.ed}tail.0.{2 * j}" in self.c:
+            cur, gh, gw = self._up_fwd(j, cur, B, gh, gw), 2 * gh, 2 * gw
+            j += 1
+        return self._close_fwd(cur, B, gh, gw)
+
+    def _close_bwd(self, dy: torch.Tensor, B: int, gh: int, gw: int, nt: int) -> torch.Tensor:
+        """dy (B, ch, gh, gw) float32 -> g.p<nt> [B*gh*gw][64], the gradient of the closing convolution's input"""
+        e = self.ed
+        ct = self.c[e + "tail.1"]
         assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (B, ct.cout, gh, gw)
         dcur = self._buf(f"g.p{nt}", (B * gh * gw, 64))
         if self.f_o[0] == "direct":
@@ -385,39 +427,66 @@ class SRBranch:
             do = self._buf("g.o", (B * gh * gw, ct.np_))
             ops.rows_from_nchw_f32(dy, do, B, ct.cout, gh, gw)
             self._conv_bwd(e + "tail.1", do, ct.np_, self.f_o, gh, gw, B * gh * gw, dcur)
-        for j in reversed(range(nt)):
-            fj, hj, wj = self.f_t[j]
-            dsrc = self._buf(f"g.p{j}", (B * hj * wj, 64))
-            if fj[0] == "direct":
-                # the four planes of the fine gradient are read in place: weight / bias gradient rows 4 c + p, and the input gradient
-                # summed over the planes (launch p adds to what launches < p stored: the residual operand is the output itself)
-                name, cj = f"{e}tail.0.{2 * j}", c[f"{e}tail.0.{2 * j}"]
-                scr = self._buf("c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
-                for pl in range(4):
-                    if self._wg(name):
-                        ops.conv3_c64_wgrad(dcur, fj[1], self.g[name + ".weight"], self.g[name + ".bias"], scr, B, hj, wj,
-                                            geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
-                    ops.conv3_c64_fwd(dcur, cj.wTp[pl], dsrc, B, hj, wj, flip=True, resid=dsrc if pl else None,
-                                      geo=ops.conv3_geo(inp=(2, pl >> 1, pl & 1)))
-            else:
-                dz = self._buf(f"g.z{j}", (B * hj * wj, 256))
-                ops.pixel_shuffle2(dcur, dz, B, hj, wj, 64, inverse=True)
-                self._conv_bwd(f"{e}tail.0.{2 * j}", dz, 256, fj, hj, wj, B * hj * wj, dsrc)
-            dcur = dsrc
-        d_rb = dcur            # d(closing-conv output + head output): the head receives it directly and through the residual chain
-        dr = self._buf("g.r", (M1, 64))
-        self._conv_bwd(f"{e}body.{self.depth}", d_rb, 64, self.f_b, H, W, M1, dr)
-        for i in reversed(range(self.depth)):
-            f0, f2, u = self.f_rb[i]
-            du = self._buf("g.u", (M1, 64))
-            self._conv_bwd(f"{e}body.{i}.body.2", dr, 64, f2, H, W, M1, du, drelu_aux=u)
-            drn = self._buf(f"g.r{i % 2}", (M1, 64))
-            self._conv_bwd(f"{e}body.{i}.body.0", du, 64, f0, H, W, M1, drn, resid=dr)
-            dr = drn
+        return dcur
+
+    def _up_bwd(self, j: int, dcur: torch.Tensor, B: int) -> torch.Tensor:
+        """dcur: the gradient of stage j's shuffled output -> g.p<j>, the gradient of its input"""
+        e, c = self.ed, self.c
+        fj, hj, wj = self.f_t[j]
+        dsrc = self._buf(f"g.p{j}", (B * hj * wj, 64))
+        if fj[0] == "direct":
+            # the four planes of the fine gradient are read in place: weight / bias gradient rows 4 c + p, and the input gradient
+            # summed over the planes (launch p adds to what launches < p stored: the residual operand is the output itself)
+            name, cj = f"{e}tail.0.{2 * j}", c[f"{e}tail.0.{2 * j}"]
+            scr = self._buf("c64.scratch", (ops.conv3_c64_wgrad_scratch_floats(),), torch.float32)
+            for pl in range(4):
+                if self._wg(name):
+                    ops.conv3_c64_wgrad(dcur, fj[1], self.g[name + ".weight"], self.g[name + ".bias"], scr, B, hj, wj,
+                                        geo=ops.conv3_geo(w_row=(4, pl), out=(2, pl >> 1, pl & 1)))
+                ops.conv3_c64_fwd(dcur, cj.wTp[pl], dsrc, B, hj, wj, flip=True, resid=dsrc if pl else None,
+                                  geo=ops.conv3_geo(inp=(2, pl >> 1, pl & 1)))
+        else:
+            dz = self._buf(f"g.z{j}", (B * hj * wj, 256))
+            ops.pixel_shuffle2(dcur, dz, B, hj, wj, 64, inverse=True)
+            self._conv_bwd(f"{e}tail.0.{2 * j}", dz, 256, fj, hj, wj, B * hj * wj, dsrc)
+        return dsrc
+
+    def _body_close_bwd(self, d_rb: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        dr = self._buf("g.r", (B * H * W, 64))
+        self._conv_bwd(f"{self.ed}body.{self.depth}", d_rb, 64, self.f_b, H, W, B * H * W, dr)
+        return dr
+
+    def _resblock_bwd(self, i: int, dr: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """dr: the gradient of ResBlock i's output -> g.r<i % 2>, the gradient of its input (the residual path's added)"""
+        e, M1 = self.ed, B * H * W
+        f0, f2, u = self.f_rb[i]
+        du = self._buf("g.u", (M1, 64))
+        self._conv_bwd(f"{e}body.{i}.body.2", dr, 64, f2, H, W, M1, du, drelu_aux=u)
+        drn = self._buf(f"g.r{i % 2}", (M1, 64))
+        self._conv_bwd(f"{e}body.{i}.body.0", du, 64, f0, H, W, M1, drn, resid=dr)
+        return drn
+
+    def _head_bwd(self, dr: torch.Tensor, d_rb: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """dr (the residual chain's gradient at the head output) += d_rb (the closing skip's); then the head convolution's
+        gradients -> g.ein"""
+        M1 = B * H * W
         ops.add_rows(dr, d_rb, M1, 64)
         dx = self._buf("g.ein", (M1, 64))
-        self._conv_bwd(e + "head.0", dr, 64, self.f_h, H, W, M1, dx)
+        self._conv_bwd(self.ed + "head.0", dr, 64, self.f_h, H, W, M1, dx)
         return dx
+
+    def edsr_backward(self, dy: torch.Tensor) -> torch.Tensor:
+        """dy (B, ch, 8H, 8W) float32 -> d(input) [B*H*W][64]."""
+        B, H, W = self.egeo
+        nt = len(self.f_t)
+        dcur = self._close_bwd(dy, B, H << nt, W << nt, nt)
+        for j in reversed(range(nt)):
+            dcur = self._up_bwd(j, dcur, B)
+        d_rb = dcur            # d(closing-conv output + head output): the head receives it directly and through the residual chain
+        dr = self._body_close_bwd(d_rb, B, H, W)
+        for i in reversed(range(self.depth)):
+            dr = self._resblock_bwd(i, dr, B, H, W)
+        return self._head_bwd(dr, d_rb, B, H, W)
 
     # ------------------------------------------------------------------ DeepLab.forward (deeplabedsr.py:61-73)
     def forward(self, low_parts, x_parts, B, H, W):
