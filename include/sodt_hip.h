@@ -153,6 +153,16 @@ typedef struct {
 
 int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_stream_t st);
 
+/* The same for the 192 -> 576 nn.Linear (csrc/linbwd.hip; autograd of backbone_vit.py:968 attn.qkv), bf16 only, N = 576, K = 192:
+ *   dX[M][192]   = dY[M][576] @ W           wT [192][576], the [N][K] operand sodt_gemm_nt takes; bit-identical to its dX
+ *   dW[576][192] (f32) += dY^T @ X[M][192]
+ *   dbias[576]   (f32) += column sums of dY (NULL: skipped)
+ * K is cut into three slabs of 64 columns and three workgroups share each of the `splits` M-slices (grid 3 * splits); each streams
+ * the slice's dY rows, the second and third read being served by the L2 of their XCD.  flags must be 0.  Alignments, splits /
+ * partial / partial_floats as above with N = 576 (splits * 576 * 192 floats of partial tiles, splits * 576 more for dbias);
+ * ldy, ldw >= 576, ldx, lddx, lddw >= 192.  Anything else: SODT_EINVAL, nothing written (callers run sodt_gemm_tn + sodt_gemm_nt). */
+int sodt_linear_bwd_wide(const sodt_linbwd_args* g, int dtype, sodt_stream_t st);
+
 /* LayerNorm over the last dim, eps 1e-5 (backbone_vit.py:1090,1128,858).  y and stats
  * (mean, rstd per row, f32 [M][2]) are written; C % (16 bytes) == 0. */
 int sodt_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,

@@ -322,12 +322,13 @@ __global__ __launch_bounds__(512) void linbwd_sq_kernel(const sodt_linbwd_args g
 
 // dW[n][k] += sum over the live slices of partial[s][n][k] (and dbias[n] += sum of bpartial[s][n]): 64 float4 columns per
 // workgroup, the slices dealt over its four waves in a fixed order and combined through LDS in a fixed order
+// (nrow rows of dW: 192 for the square layer, 576 for the wide one; the bias blocks follow the wblocks tile blocks)
 __global__ __launch_bounds__(256) void linbwd_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dW, int lddw, int live,
-                                                           const float* __restrict__ bpartial, float* __restrict__ dbias, int wblocks) {
+                                                           const float* __restrict__ bpartial, float* __restrict__ dbias, int wblocks, int nrow) {
   __shared__ float4 red[4][64];
   const bool bias = (int)blockIdx.x >= wblocks;
   const float* src = bias ? bpartial : partial;
-  const long slice = bias ? LB_C : (long)LB_C * LB_C;
+  const long slice = bias ? nrow : (long)nrow * LB_C;
   const long n4 = slice / 4;
   const int c = threadIdx.x & 63, sg = threadIdx.x >> 6;
   const long i = (long)(bias ? (int)blockIdx.x - wblocks : (int)blockIdx.x) * 64 + c;
@@ -365,6 +366,262 @@ int launch_linbwd(const sodt_linbwd_args* g, float* partial, float* bpartial, hi
   return sodt_launch<linbwd_sq_kernel<DG>>(dim3((unsigned)g->splits), dim3(512), LB_LDS, st, *g, partial, bpartial);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The wide form: backward of the 192 -> 576 linear layer (attn.qkv), dX[M][192] = dY[M][576] @ W, dW[576][192] += dY^T @ X.
+// wT [192][576] (216 KiB) and the dW accumulator (442 KB) do not fit one CU, so K = 192 (the columns of dX, X and dW) is cut into
+// three slabs of 64 and THREE sibling workgroups share an M-slice: workgroup (slice, slab j) streams all 576 columns of dY for
+// its rows plus X[:, 64 j .. 64 j + 63], keeps wT rows 64 j .. 64 j + 63 resident (72 KiB) and produces dX[:, slab j] (the
+// contraction over N is whole: no cross-workgroup sum) and the slice's partial dW[:, slab j].  The siblings are consecutive
+// logical ids of xcd_remap, so they run on one XCD at the same time and two of the three dY reads are served by its L2.
+//   * Stages of 32 rows: dY image [32][576] (36 KiB) then X-slab image [32][64] (4 KiB), two slots.  Waves 4-7 bring a stage in
+//     ten 1 KiB LDS-DMA pieces each (the images are contiguous: piece I lands at I KiB of the slot; pieces 0-35 dY, 36-39 X) and
+//     hold nothing else in the vector-memory queue, so the count they wait for at the top of stage s - everything they have in
+//     flight, DMA(s) - is exact; DMA(s + 1) goes out right after the barrier, into the slot every wave has just left.
+//   * Waves 0-3 (c = wid & 1, u = wid >> 1) form the 16 x 32 block of dX at rows 16 u, slab columns 32 c: 18 contraction steps
+//     of 32 (N ascending, the order of gemm_nt3_kernel), fragments read two steps ahead of their MFMAs behind counted lgkmcnt
+//     waits; the W rows are permuted as in the square kernel, so a lane stores 16 bytes.  They never wait on vector memory.
+//   * All eight waves, as a 4 (n) x 2 (k) grid, add dY^T X into 9 x 2 accumulator tiles each (n units 9 wr .. 9 wr + 8, slab
+//     columns 32 wc ..); dbias of the n units 12 j .. 12 j + 11 belongs to slab j (ones-vector MFMA, the units of a wave row
+//     alternating between its two waves).
+// The swizzles are the square kernel's: every row pitch here (1152 and 128 bytes) is 128 modulo 256 like its 384.
+constexpr int LW_N = 576, LW_KS = 64;
+constexpr int LW_YROWB = LW_N * 2;                    // 1152 bytes per row of the dY image and of the wT slab
+constexpr int LW_XROWB = LW_KS * 2;                   // 128 bytes per row of the X-slab image
+constexpr int LW_WBYTES = LW_KS * LW_YROWB;           // 72 KiB
+constexpr int LW_YIMG = LB_ROWS * LW_YROWB;           // 36 KiB
+constexpr int LW_XIMG = LB_ROWS * LW_XROWB;           // 4 KiB
+constexpr int LW_STAGE = LW_YIMG + LW_XIMG;           // 40 KiB
+constexpr int LW_NST = 2;
+constexpr int LW_LDS = LW_WBYTES + LW_NST * LW_STAGE; // 152 KiB
+constexpr int LW_NDMA = 10;                           // DMA pieces per loader wave and stage
+constexpr int LW_YPIECES = LW_YIMG / 1024;            // 36
+
+template <int ROWB> __device__ __forceinline__ u32x4 lw_frag_tr(uint32_t addr) {
+  const uint2 lo = lb_rd_tr<0>(addr), hi = lb_rd_tr<4 * ROWB>(addr);
+  u32x4 r; r.x = lo.x; r.y = lo.y; r.z = hi.x; r.w = hi.y;
+  return r;
+}
+#define LW_LGKM(N) do { asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
+__global__ __launch_bounds__(512) void linbwd_wide_kernel(const sodt_linbwd_args g, float* __restrict__ partial, float* __restrict__ bpartial) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wid >> 1, wc = wid & 1;
+  const int fr = lane & 15, fg = lane >> 4;
+  const uint32_t lbase = lb_lds_addr(dsm);
+
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
+  const int split = lid / 3, slab = lid - 3 * split;
+  const long rows_per = (((g.M + g.splits - 1) / g.splits) + LB_ROWS - 1) / LB_ROWS * LB_ROWS;
+  const long mbeg = (long)split * rows_per;
+  const long mend = (mbeg + rows_per < g.M) ? (mbeg + rows_per) : g.M;
+  if (mbeg >= mend) return;                   // dead slice
+  const int nrows = (int)(mend - mbeg);
+  const int nsteps = (nrows + LB_ROWS - 1) / LB_ROWS;
+
+  // ---- resident wT slab: rows 64 slab .. + 63 (output columns of dX), 72 chunks of 16 bytes each, chunk c of row r at
+  //      r * 1152 + ((c ^ f(r)) << 4) (4,608 chunks = 9 per thread)
+  {
+    uint4 wv[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+      const int id = tid + 512 * e, r = id / 72, c = id - r * 72;
+      wv[e] = *(const uint4*)((const bf16*)g.wT + (long)(LW_KS * slab + r) * g.ldw + 8 * c);
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+      const int id = tid + 512 * e, r = id / 72, c = id - r * 72;
+      const int f = ((r >> 1) & 1) | (((r >> 3) & 3) << 1);
+      *(uint4*)(dsm + r * LW_YROWB + ((c ^ f) << 4)) = wv[e];
+    }
+  }
+  __syncthreads();                            // (no DMA in flight yet: a plain barrier)
+
+  // ---- DMA descriptors of the loader waves 4-7: piece I = 10 (wid - 4) + e, chunk id = 64 I + lane (dY: row id / 72; X: row
+  //      (id - 2304) / 8); the source column carries the swizzle of the 32-byte unit
+  const unsigned char* zero = (const unsigned char*)lb_zero16;
+  const bool loader = wid >= 4;
+  const int piece0 = LW_NDMA * (wid & 3);
+  const long ystep = (long)LB_ROWS * g.ldy * 2, xstep = (long)LB_ROWS * g.ldx * 2;
+  const unsigned char* cur[LW_NDMA];
+  int drow[LW_NDMA];
+#pragma unroll
+  for (int e = 0; e < LW_NDMA; ++e) {
+    const int I = piece0 + e;
+    const bool isx = I >= LW_YPIECES;
+    const int idy = 64 * I + lane, idx = idy - 64 * LW_YPIECES;
+    const int r2 = isx ? (idx >> 3) : idy / 72;
+    const int c2 = isx ? (idx & 7) : idy - r2 * 72;
+    const int sw2 = ((r2 >> 1) & 1) | (((r2 >> 3) & 1) << 1);
+    const int col = ((((c2 >> 1) ^ sw2) << 1) | (c2 & 1)) << 3;
+    drow[e] = r2;
+    cur[e] = isx ? (const unsigned char*)((const bf16*)g.X + (mbeg + r2) * g.ldx + LW_KS * slab + col)
+                 : (const unsigned char*)((const bf16*)g.dY + (mbeg + r2) * g.ldy + col);
+  }
+
+  // ---- dW fragments: lane (fg, q = fr >> 2, p = fr & 3) reads 8 bytes of LDS row 8 fg + q (+4); wave (wr, wc) owns dW rows
+  //      n = 144 wr .. + 143 (nine 16-column units of the dY image) and slab columns 32 wc .. + 31 (two units of the X image)
+  const int q_ = fr >> 2, p_ = fr & 3;
+  const int frow = 8 * fg + q_;
+  const int swQ = (q_ >> 1) | ((fg & 1) << 1);
+  uint32_t pa[9], qa[2];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) pa[i] = lbase + LW_WBYTES + frow * LW_YROWB + 8 * p_ + (((wr * 9 + i) ^ swQ) << 5);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) qa[j] = lbase + LW_WBYTES + LW_YIMG + frow * LW_XROWB + 8 * p_ + (((wc * 2 + j) ^ swQ) << 5);
+
+  // ---- dX fragments (waves 0-3): dY rows by ds_read_b128 (lane (fr, fg): row 16 u + fr, n = 32 ks + 8 fg ..), wT slab rows
+  //      32 c + 8 (fr >> 2) + (fr & 3) (+4 for the second tile of the pair)
+  const bool nt_wave = wid < 4;
+  const int xc = wid & 1, xu = (wid >> 1) & 1;
+  const int s2 = ((fr >> 1) & 1) | (((fr >> 3) & 1) << 1);
+  const uint32_t yrow = lbase + LW_WBYTES + (16 * xu + fr) * LW_YROWB + ((fg & 1) << 4);
+  const uint32_t yRd0 = yrow + (((fg >> 1) ^ s2) << 5);                // ks even
+  const uint32_t yRd1 = yrow + (((2 + (fg >> 1)) ^ s2) << 5);          // ks odd
+  const int fW = ((fr >> 1) & 1) | (((fr >> 2) & 3) << 1);
+  const int wrow = 32 * xc + 8 * (fr >> 2) + (fr & 3);
+  const uint32_t wRd0 = lbase + wrow * LW_YROWB + ((fg ^ fW) << 4);
+  const uint32_t wRd1 = lbase + wrow * LW_YROWB + (((4 + fg) ^ fW) << 4);
+  const int ocol = LW_KS * slab + 32 * xc + 8 * fg;          // first of this lane's 8 dX columns
+
+  // dbias: n unit U belongs to slab U / 12; inside wave row wr the units alternate between wc = 0 (i even) and wc = 1 (i odd)
+  const bool do_bias = g.dbias != nullptr;
+  u32x4 ones; ones.x = ones.y = ones.z = ones.w = 0x3F803F80u;
+
+  f32x4 acc[9][2], bacc[5];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 5; ++i) bacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (loader) {
+    const uint32_t dst = LW_WBYTES + piece0 * 1024;
+#pragma unroll
+    for (int e = 0; e < LW_NDMA; ++e) {
+      const unsigned char* s = drow[e] < nrows ? cur[e] : zero;
+      __builtin_amdgcn_global_load_lds((glb_void*)s, (lds_void*)(dsm + dst + e * 1024), 16, 0, 0);
+      cur[e] += (piece0 + e >= LW_YPIECES) ? xstep : ystep;
+    }
+  }
+  int slot = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    // loader waves: DMA(s) is all they have in flight; the other waves have only dX stores there and wait for nothing
+    if (loader) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const uint32_t so = slot * LW_STAGE;
+
+    if (loader) {
+      if (s + 1 < nsteps) {                    // stage s + 1 -> the other slot: last read in iteration s - 1
+        const uint32_t dst = LW_WBYTES + (slot ^ 1) * LW_STAGE + piece0 * 1024;
+        const int rel = (s + 1) * LB_ROWS;
+        if (rel + LB_ROWS <= nrows) {
+#pragma unroll
+          for (int e = 0; e < LW_NDMA; ++e) {
+            __builtin_amdgcn_global_load_lds((glb_void*)cur[e], (lds_void*)(dsm + dst + e * 1024), 16, 0, 0);
+            cur[e] += (piece0 + e >= LW_YPIECES) ? xstep : ystep;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < LW_NDMA; ++e) {
+            const unsigned char* sp = rel + drow[e] < nrows ? cur[e] : zero;
+            __builtin_amdgcn_global_load_lds((glb_void*)sp, (lds_void*)(dsm + dst + e * 1024), 16, 0, 0);
+            cur[e] += (piece0 + e >= LW_YPIECES) ? xstep : ystep;
+          }
+        }
+      }
+    } else {
+      f32x4 na0 = f32x4{0.f, 0.f, 0.f, 0.f}, na1 = na0;
+      u32x4 fyA0, fyB0, fw0A0, fw1A0, fw0B0, fw1B0, fyA1, fyB1, fw0A1, fw1A1, fw0B1, fw1B1;
+      // group G = contraction steps 2 G (A) and 2 G + 1 (B); buffer T
+#define LW_NT_RD(G, T)                                                                                \
+      fyA##T = lb_rd128<128 * (G)>(yRd0 + so); fyB##T = lb_rd128<128 * (G)>(yRd1 + so);                \
+      fw0A##T = lb_rd128<128 * (G)>(wRd0); fw1A##T = lb_rd128<128 * (G) + 4 * LW_YROWB>(wRd0);         \
+      fw0B##T = lb_rd128<128 * (G)>(wRd1); fw1B##T = lb_rd128<128 * (G) + 4 * LW_YROWB>(wRd1);
+#define LW_NT_MM(T)                                                                                   \
+      lb_mma(na0, fw0A##T, fyA##T); lb_mma(na1, fw1A##T, fyA##T);                                     \
+      lb_mma(na0, fw0B##T, fyB##T); lb_mma(na1, fw1B##T, fyB##T);
+      LW_NT_RD(0, 0)
+      LW_NT_RD(1, 1) LW_LGKM(6); LW_NT_MM(0)
+      LW_NT_RD(2, 0) LW_LGKM(6); LW_NT_MM(1)
+      LW_NT_RD(3, 1) LW_LGKM(6); LW_NT_MM(0)
+      LW_NT_RD(4, 0) LW_LGKM(6); LW_NT_MM(1)
+      LW_NT_RD(5, 1) LW_LGKM(6); LW_NT_MM(0)
+      LW_NT_RD(6, 0) LW_LGKM(6); LW_NT_MM(1)
+      LW_NT_RD(7, 1) LW_LGKM(6); LW_NT_MM(0)
+      LW_NT_RD(8, 0) LW_LGKM(6); LW_NT_MM(1)
+      LW_LGKM(0); LW_NT_MM(0)
+#undef LW_NT_RD
+#undef LW_NT_MM
+      // lane (fg, fr): row 16 u + fr of the stage, columns ocol .. ocol + 7 (tile 0: + 0..3, tile 1: + 4..7)
+      const int r0 = s * LB_ROWS + 16 * xu + fr;
+      float v[8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { v[r] = na0[r]; v[4 + r] = na1[r]; }
+      if (r0 < nrows) *(uint4*)((bf16*)g.dX + (mbeg + r0) * g.lddx + ocol) = pack<bf16>(v);
+    }
+
+    {
+      u32x4 fp[9], fq[2];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) fp[i] = lw_frag_tr<LW_YROWB>(pa[i] + so);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fq[j] = lw_frag_tr<LW_XROWB>(qa[j] + so);
+      LB_LGKM0();
+#pragma unroll
+      for (int i = 0; i < 9; ++i) { lb_mma(acc[i][0], fp[i], fq[0]); lb_mma(acc[i][1], fp[i], fq[1]); }
+      if (do_bias) {
+        if (wc == 0) {
+#pragma unroll
+          for (int ii = 0; ii < 5; ++ii)
+            if ((wr * 9 + 2 * ii) / 12 == slab) lb_mma(bacc[ii], fp[2 * ii], ones);
+        } else {
+#pragma unroll
+          for (int ii = 0; ii < 4; ++ii)
+            if ((wr * 9 + 2 * ii + 1) / 12 == slab) lb_mma(bacc[ii], fp[2 * ii + 1], ones);
+        }
+      }
+    }
+    slot ^= 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+
+  // acc[i][j][r]: dW row n = 144 wr + 16 i + 4 fg + r, column k = 64 slab + 32 wc + 16 j + fr
+  const int kcol = LW_KS * slab + 32 * wc + fr;
+  if (partial) {
+    float* part = partial + (long)split * LW_N * LB_C + (long)(wr * 144 + 4 * fg) * LB_C + kcol;
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part[(16 * i + r) * LB_C + 16 * j] = acc[i][j][r];
+  } else {
+    float* d = g.dW + (long)(wr * 144 + 4 * fg) * g.lddw + kcol;
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) atomicAdd(d + (long)(16 * i + r) * g.lddw + 16 * j, acc[i][j][r]);
+  }
+  if (do_bias && fr == 0) {          // bacc[ii][r]: unit i = 2 ii + wc, row 4 fg + r <-> n, all columns equal
+#pragma unroll
+    for (int ii = 0; ii < 5; ++ii) {
+      const int i = 2 * ii + wc;
+      if (i < 9 && (wr * 9 + i) / 12 == slab) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int n = wr * 144 + 16 * i + 4 * fg + r;
+          if (bpartial) bpartial[(long)split * LW_N + n] = bacc[ii][r];
+          else atomicAdd(g.dbias + n, bacc[ii][r]);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_stream_t st) {
@@ -391,5 +648,27 @@ extern "C" int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_str
   const int live = (int)(((long)g->M + rows_per - 1) / rows_per);
   const int wblocks = LB_C * LB_C / 4 / 64;
   return sodt_launch<linbwd_reduce_kernel>(dim3(wblocks + (bpartial ? 1 : 0)), dim3(256), 0, (hipStream_t)st, (const float*)partial,
-                                           g->dW, g->lddw, live, (const float*)bpartial, g->dbias, wblocks);
+                                           g->dW, g->lddw, live, (const float*)bpartial, g->dbias, wblocks, LB_C);
+}
+
+extern "C" int sodt_linear_bwd_wide(const sodt_linbwd_args* g, int dtype, sodt_stream_t st) {
+  if (!g || dtype != SODT_BF16 || g->N != LW_N || g->K != LB_C || g->M <= 0 || g->splits < 1 || g->splits > 21845) return SODT_EINVAL;
+  if (!g->dY || !g->X || !g->wT || !g->dX || !g->dW || g->flags != 0) return SODT_EINVAL;
+  if ((g->ldy % 8) || (g->ldx % 8) || (g->ldw % 8) || (g->lddx % 8) || (g->lddw % 4)) return SODT_EINVAL;
+  if (g->ldy < LW_N || g->ldx < LB_C || g->ldw < LW_N || g->lddx < LB_C || g->lddw < LB_C) return SODT_EINVAL;
+  if ((((uintptr_t)g->dY) | ((uintptr_t)g->X) | ((uintptr_t)g->wT) | ((uintptr_t)g->dX) | ((uintptr_t)g->dW)) & 15) return SODT_EINVAL;
+  if (g->dbias && (((uintptr_t)g->dbias) & 15)) return SODT_EINVAL;
+  // the scratch protocol of sodt_linear_bwd_sq with N = 576: splits * N * K floats of partial tiles, then splits * N of dbias rows
+  const long tile_floats = (long)g->splits * LW_N * LB_C;
+  const bool use_partial = g->partial && g->splits > 1 && tile_floats <= g->partial_floats && (((uintptr_t)g->partial) & 15) == 0;
+  float* partial = use_partial ? g->partial : nullptr;
+  float* bpartial = (use_partial && g->dbias && tile_floats + (long)g->splits * LW_N <= g->partial_floats) ? g->partial + tile_floats : nullptr;
+  // three sibling workgroups per slice, consecutive logical ids
+  const int rc = sodt_launch<linbwd_wide_kernel>(dim3(3u * (unsigned)g->splits), dim3(512), LW_LDS, (hipStream_t)st, *g, partial, bpartial);
+  if (rc || !use_partial) return rc;
+  const long rows_per = ((((long)g->M + g->splits - 1) / g->splits) + LB_ROWS - 1) / LB_ROWS * LB_ROWS;
+  const int live = (int)(((long)g->M + rows_per - 1) / rows_per);
+  const int wblocks = LW_N * LB_C / 4 / 64;
+  return sodt_launch<linbwd_reduce_kernel>(dim3(wblocks + (bpartial ? (LW_N / 4 + 63) / 64 : 0)), dim3(256), 0, (hipStream_t)st,
+                                           (const float*)partial, g->dW, g->lddw, live, (const float*)bpartial, g->dbias, wblocks, LW_N);
 }

@@ -161,6 +161,7 @@ class BlockRoute(NamedTuple):
     mlp: str                            # MLP_*
     zscratch: bool                      # window above 64 tokens: the five-launch attention backward needs its zeroed scratch
     sq_ok: bool                         # attn.proj / fc2 backward may take the square one-launch form (use_fused_linbwd permitting)
+    wide_ok: bool                       # attn.qkv backward may take the wide one-launch form (use_wide_linbwd permitting)
 
 
 class ConvRoute(NamedTuple):
@@ -281,6 +282,12 @@ class Engine:
         # bf16, C = 192: backward of attn.proj and of the conv-MLP's fc2 as ONE launch each (csrc/linbwd.hip: dX and dW from one read
         # of dY) against the sodt_gemm_tn + sodt_gemm_nt pair
         self.use_fused_linbwd = True
+        # bf16, C = 192: backward of attn.qkv (192 -> 576) as ONE launch, three sibling workgroups per M-slice (csrc/linbwd.hip,
+        # sodt_linear_bwd_wide), against the sodt_gemm_tn + sodt_gemm_nt pair.  The switch is read live in the backward; the row
+        # threshold is read when a block's route is recorded.  Below 85 slices x 16 stages of 32 rows the launch cannot give its
+        # 255 workgroups a full pipeline and would occupy a fraction of the CUs the pair fills (derived, not measured).
+        self.use_wide_linbwd = True
+        self.wide_linbwd_min_rows = 85 * 512
         # bf16: the Detect level as one pass each way (csrc/detect.hip) against sodt_gemm_nt with the Detect epilogue and
         # sodt_detect_unpermute + sodt_gemm_tn + sodt_gemm_nt; read when a plan's backward is first recorded and at every forward
         self.use_fused_detect = True
@@ -830,7 +837,8 @@ class Engine:
         else:
             mlp = MLP_FOLD if pre in P["cmlp"] else MLP_CONV
         return BlockRoute(x_in, (B, H, W, Cc, ws, shift), pad, attn, wpk, mlp, zscratch=wpk is None and ws * ws > 64,
-                          sq_ok=pad is None and plan.dt == torch.bfloat16 and Cc == 192)
+                          sq_ok=pad is None and plan.dt == torch.bfloat16 and Cc == 192,
+                          wide_ok=plan.dt == torch.bfloat16 and Cc == 192 and attn != ATTN_PADDED and M >= self.wide_linbwd_min_rows)
 
     def _block_fwd(self, plan, P, tag, blk, x_in, B, H, W):
         ops.set_tag(tag)
@@ -945,16 +953,18 @@ class Engine:
             ops.gemm_nt([SegSpec(ca)], w[pre + "mlp.fc2.weight"], xo, M, Cc, Cc, bias=p[pre + "mlp.fc2.bias"], resid=xm)
         return xo
 
-    def _linear_bwd(self, P, name, dY, X, dX, M, N, K, *, bias=True, sq=False, dgelu_aux=None, ldy=None, y_off=0, resid=None,
-                    plan=None, need_dx=True):
+    def _linear_bwd(self, P, name, dY, X, dX, M, N, K, *, bias=True, sq=False, wide=False, dgelu_aux=None, ldy=None, y_off=0,
+                    resid=None, plan=None, need_dx=True):
         """Backward of one nn.Linear / 1x1 convolution `name` ([N][K] weight): dW (and dbias) += dY^T X by sodt_gemm_tn, then
         dX = dY W [* gelu'(dgelu_aux)] [+ resid] by sodt_gemm_nt; dY may be N columns at y_off of a wider buffer.  sq: try the
         square one-launch form first (csrc/linbwd.hip: both from one read of dY; ops.linear_bwd_sq returns False where the entry
-        point refuses the layer, and the two launches run instead).  plan: its frozen parameters take no weight-gradient launch (a
+        point refuses the layer, and the two launches run instead).  wide: the same for the 192 -> 576 layer (ops.linear_bwd_wide).  plan: its frozen parameters take no weight-gradient launch (a
         frozen weight AND bias leave the plain sodt_gemm_nt); need_dx False: nobody reads dX, only the parameter gradients run."""
         gw, gb, wT = self.g[name + ".weight"], self.g[name + ".bias"] if bias else None, P["wT"][name + ".weight"]
         wg = plan is None or plan.trainable(name + ".weight", *([name + ".bias"] if bias else []))
         if sq and wg and need_dx and ops.linear_bwd_sq(dY, X, wT, dX, gw, M, dbias=gb, dgelu_aux=dgelu_aux):
+            return
+        if wide and wg and need_dx and ops.linear_bwd_wide(dY, X, wT, dX, gw, M, dbias=gb):
             return
         if wg:
             ops.gemm_tn(dY, [SegSpec(X)], gw, M, N, K, dbias=gb, ldy=ldy, y_off=y_off)
@@ -1094,7 +1104,8 @@ class Engine:
                     ops.window_attn_bwd(b[tag + ".qkv"], bias_t, ao, dao, b[tag + ".lse"], dqkv, dbt, scratch, B, H, W, Cc, HEADS, ws, shift)
                 # (always: the transposition also clears dbt, which the next block's attention backward adds into)
                 ops.transpose_f32(dbt, g[pre + "attn.relative_position_bias_table"], HEADS, L2 * L2, accumulate=2)
-                self._linear_bwd(P, pre + "attn.qkv", dqkv, xn1, dxn, M, 3 * Cc, Cc, plan=plan, need_dx=ln1)
+                self._linear_bwd(P, pre + "attn.qkv", dqkv, xn1, dxn, M, 3 * Cc, Cc, wide=self.use_wide_linbwd and r.wide_ok, plan=plan,
+                                 need_dx=ln1)
         if ln1:
             ops.layernorm_bwd(dxn, r.x_in, b[tag + ".st1"], p[pre + "norm1.weight"], dxm, dX, g[pre + "norm1.weight"], g[pre + "norm1.bias"], M, Cc)
 

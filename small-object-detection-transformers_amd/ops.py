@@ -338,6 +338,46 @@ def linear_bwd_sq_splits(M: int) -> int:
     return max(1, min(M // 512, 256))
 
 
+def linear_bwd_wide(dY: torch.Tensor, X: torch.Tensor, wT: torch.Tensor, dX: torch.Tensor, dW: torch.Tensor, M: int, *,
+                    dbias: Optional[torch.Tensor] = None, ldy: Optional[int] = None, y_off: int = 0, ldx: Optional[int] = None,
+                    lddx: Optional[int] = None, lddw: Optional[int] = None, splits: Optional[int] = None) -> bool:
+    """dX[M][192] = dY[M][576] @ W, dW[576][192] (f32) += dY^T @ X, dbias[576] += column sums of dY, in ONE launch (plus the slice
+    reduction); wT is the [192][576] operand gemm_nt takes for the same dX.  Three sibling workgroups per M-slice, one 64-column
+    slab of K each (csrc/linbwd.hip).  Returns False, with nothing launched, written or recorded, when sodt_linear_bwd_wide does not
+    take the layer (SODT_EINVAL): the caller then runs gemm_tn + gemm_nt."""
+    if any(t.dtype != torch.bfloat16 for t in (dY, X, wT, dX)) or dW.dtype != torch.float32 or (dbias is not None and dbias.dtype != torch.float32):
+        return False
+    if tuple(wT.shape) != (192, 576) or X.shape[-1] < 192 or dX.shape[-1] < 192:
+        return False
+    g = L.LinBwdArgs()
+    g.dY = dY.data_ptr() + y_off * dY.element_size()
+    g.ldy = dY.shape[-1] if ldy is None else ldy
+    g.X, g.ldx = X.data_ptr(), (X.shape[-1] if ldx is None else ldx)
+    g.wT, g.ldw = wT.data_ptr(), wT.stride(0)
+    g.dX, g.lddx = dX.data_ptr(), (dX.shape[-1] if lddx is None else lddx)
+    g.dW, g.lddw = dW.data_ptr(), (192 if lddw is None else lddw)
+    g.dbias = _p(dbias)
+    g.M, g.N, g.K = M, 576, 192
+    g.splits = linear_bwd_wide_splits(M) if splits is None else splits
+    if _tn_scratch is not None and _tn_scratch.device == dY.device and g.splits > 1:
+        g.partial, g.partial_floats = _tn_scratch.data_ptr(), _tn_scratch.numel()
+    fn = _lib.sodt_linear_bwd_wide
+    args = (C.byref(g), L.BF16)
+    rc = fn(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc == L.EINVAL:              # refused before any launch
+        return False
+    if rc != 0:
+        raise RuntimeError(f"sodt_linear_bwd_wide failed with status {rc}")
+    if _active_recorder is not None:
+        _active_recorder.append((fn, args, "sodt_linear_bwd_wide", _tag))
+    return True
+
+
+def linear_bwd_wide_splits(M: int) -> int:
+    """M-slices of sodt_linear_bwd_wide: three workgroups per slice, 3 x 85 = 255 on 256 CUs, at least 16 stages of 32 rows per slice."""
+    return max(1, min(M // 512, 85))
+
+
 def layernorm_fwd(x, gamma, beta, y, stats, M, Cc):
     _launch("sodt_layernorm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), M, Cc, dt_code(x))
 

@@ -56,6 +56,12 @@ def cost(name, args):
         npass = 4 if g.flags & 8 else 3
         return (f"M={g.M} N={g.N} K={g.K} dX+dW{' dgelu' if g.flags & 8 else ''}",
                 g.M * npass * g.N * ES + (2.0 * g.splits + 2) * g.N * g.K * 4 + g.N * g.K * ES, 4.0 * g.M * g.N * g.K)
+    if name == "sodt_linear_bwd_wide":
+        g = unwrap(args[0])
+        # the single-pass model: dY (N wide) and X (K wide) in once, dX out; the second and third sibling's dY reads are priced as
+        # L2 hits.  One partial dW tile per slice written and read, dW itself, the weight once
+        return (f"M={g.M} N={g.N} K={g.K} dX+dW wide", g.M * (g.N + 2 * g.K) * ES + (2.0 * g.splits + 2) * g.N * g.K * 4 + g.N * g.K * ES,
+                4.0 * g.M * g.N * g.K)
     if name in ("sodt_detect_fwd", "sodt_detect_bwd"):
         g = unwrap(args[0])
         M, N = g.B * g.HW, g.na * g.no
