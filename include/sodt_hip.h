@@ -163,6 +163,28 @@ int sodt_linear_bwd_sq(const sodt_linbwd_args* g, int dtype, sodt_stream_t st);
  * ldy, ldw >= 576, ldx, lddx, lddw >= 192.  Anything else: SODT_EINVAL, nothing written (callers run sodt_gemm_tn + sodt_gemm_nt). */
 int sodt_linear_bwd_wide(const sodt_linbwd_args* g, int dtype, sodt_stream_t st);
 
+/* Backward of the linear MLP fc2(GELU(fc1(xn))) at C = 192, hidden 768, around one pass over xn and dY (csrc/mlpbwd.hip; autograd of
+ * backbone_vit.py:884-890), bf16 only:
+ *   h = xn[M][192] @ w1^T + b1 (recomputed, not stored)   w1 = fc1.weight [768][192], b1 = fc1.bias (f32)
+ *   dh[M][768]    = (dY[M][192] @ fc2.weight) * gelu'(h)  w2T [768][192] with w2T[n][c] = fc2.weight[c][n], the [N][K] operand
+ *                                                         sodt_gemm_nt takes; bit-identical to sodt_gemm_nt's SODT_EPI_BIAS |
+ *                                                         SODT_EPI_DGELU_RC over [xn | dY] and [w1 | w2T]
+ *   hact[M][768]  = GELU(h), sodt_mlp_fwd's logistic form (NULL: not written)
+ *   dW1[768][192] += dh^T @ xn,      db1[768] += column sums of dh         (f32)
+ *   dW2[192][768] += dY^T @ GELU(h), db2[192] += column sums of dY         (f32; GELU(h) rounded to bf16 as hact holds it)
+ * The hidden dimension is cut into eight slabs of 96 columns and eight workgroups share each of the `splits` M-slices (grid
+ * 8 * splits); each streams the slice's xn and dY rows, seven of the eight reads being served by the L2 of their XCD.
+ * Every bf16 operand 16-byte aligned with a leading dimension that is a multiple of 8 elements and at least its width; the f32
+ * operands 16-byte aligned, lddw1 >= 192 and lddw2 >= 768 multiples of 4.  partial / partial_floats: as in sodt_gemm_tn_args with
+ * 2 * splits * 147,456 floats of partial tiles (summed in a fixed order: run-to-run deterministic) and splits * 960 more for the
+ * two bias rows; a scratch too small for the tiles (or splits == 1): f32 atomics.
+ * C other than 192, float32, a NULL operand other than hact, any other alignment: SODT_EINVAL, nothing written (callers run
+ * sodt_gemm_tn + sodt_gemm_nt + sodt_gemm_tn).  The arguments are plain parameters, as sodt_mlp_fwd's. */
+int sodt_mlp_bwd(const void* xn, int ldxn, const void* dY, int ldy, const void* w1, int ldw1, const float* b1,
+                 const void* w2T, int ldw2, void* dh, int lddh, void* hact, int ldha, float* dW1, int lddw1, float* db1,
+                 float* dW2, int lddw2, float* db2, long M, int C, int splits, float* partial, long partial_floats,
+                 int dtype, sodt_stream_t st);
+
 /* LayerNorm over the last dim, eps 1e-5 (backbone_vit.py:1090,1128,858).  y and stats
  * (mean, rstd per row, f32 [M][2]) are written; C % (16 bytes) == 0. */
 int sodt_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,

@@ -160,6 +160,7 @@ SIGNATURES = {
     "sodt_gemm_tn": [C.POINTER(GemmTnArgs), _I, _P],
     "sodt_linear_bwd_sq": [C.POINTER(LinBwdArgs), _I, _P],
     "sodt_linear_bwd_wide": [C.POINTER(LinBwdArgs), _I, _P],
+    "sodt_mlp_bwd": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _L, _I, _I, _P, _L, _I, _P],
     "sodt_layernorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sodt_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "sodt_window_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -66,22 +66,7 @@ __device__ __forceinline__ f32x4 mma(const u32x4& w, const u32x4& a, const f32x4
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(uw.v, ua.v, c, 0, 0, 0);
 }
 
-// GELU of the fused kernel: x Phi(x) with Phi(x) ~ 1 / (1 + 2^(xc (A0 + A1 xc^2 + A2 xc^4))), xc = x clamped to +-8 - the logistic
-// ("tanh") form with a quartic term, its three constants fitted to the exact erf GELU (nn.GELU() default, backbone_vit.py:872):
-// max |error| 2.5e-5 over the whole line (the odd degree-15 erf polynomial of the GEMM epilogues: 1.4e-4; one bf16 ulp at 1: 3.9e-3).
-// 7 FMA-pipe instructions + v_exp_f32 + v_rcp_f32 per element instead of 13: the kernel is bound by instruction ISSUE (per step a
-// SIMD's two waves needed 2 x (880 VALU + 384 MFMA + 300 LDS) issue cycles against 1,536 matrix-pipe cycles, stamps in
-// profiles/r05_mlp_stamps.md), and the activation was more than half of it.  (A two-constant fit, 2.7e-4, is two instructions
-// shorter but its error is a smooth bias, not rounding noise: it moved the p95 of the model's gradient-error ratio against the
-// reference's own autocast from 1.36 to 1.51 - tests/test_bf16_parity_gpu.py - and was dropped.)  |x| > 8: 2^(+-40) -> -0 or x.
-__device__ __forceinline__ float gelu_sig(float x) {
-  const float xc = __builtin_amdgcn_fmed3f(x, -8.0f, 8.0f);
-  const float u = xc * xc;
-  const float t = fmaf(fmaf(u, 0.001014263f, -0.10677572f), u, -2.3011212f);
-  const float e = __builtin_amdgcn_exp2f(xc * t);
-  return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
+// (gelu_sig, the logistic GELU of this kernel, lives in common.h: csrc/mlpbwd.hip recomputes the same activation)
 struct MlpArgs {
   const bf16* xn; const bf16* w1; const float* b1; const bf16* w2; const float* b2; const bf16* resid;
   bf16* out; bf16* hact; long M;

@@ -162,6 +162,7 @@ class BlockRoute(NamedTuple):
     zscratch: bool                      # window above 64 tokens: the five-launch attention backward needs its zeroed scratch
     sq_ok: bool                         # attn.proj / fc2 backward may take the square one-launch form (use_fused_linbwd permitting)
     wide_ok: bool                       # attn.qkv backward may take the wide one-launch form (use_wide_linbwd permitting)
+    mlp_bwd: bool = False               # MLP_FUSED only: the backward is sodt_mlp_bwd's one launch and the forward keeps no GELU(h)
 
 
 class ConvRoute(NamedTuple):
@@ -288,6 +289,13 @@ class Engine:
         # 255 workgroups a full pipeline and would occupy a fraction of the CUs the pair fills (derived, not measured).
         self.use_wide_linbwd = True
         self.wide_linbwd_min_rows = 85 * 512
+        # bf16, C = 192, MLP_FUSED: dh, dW1 / db1 and dW2 / db2 from ONE launch that recomputes GELU(h) (csrc/mlpbwd.hip, sodt_mlp_bwd:
+        # eight sibling workgroups per M-slice, one 96-column slab of the hidden dimension each) against sodt_gemm_tn +
+        # sodt_gemm_nt(DGELU_RC) + sodt_gemm_tn; the forward then writes no GELU(h).  Both the switch and the threshold are read when a
+        # block's route is recorded (the forward has to know whether GELU(h) is kept).  Below 32 slices x 64 stages of 32 rows the
+        # one-off 72 KiB load of the weight slabs is not amortised (derived, not measured).
+        self.use_fused_mlp_bwd = True
+        self.mlp_bwd_min_rows = 32 * 64 * 32
         # bf16: the Detect level as one pass each way (csrc/detect.hip) against sodt_gemm_nt with the Detect epilogue and
         # sodt_detect_unpermute + sodt_gemm_tn + sodt_gemm_nt; read when a plan's backward is first recorded and at every forward
         self.use_fused_detect = True
@@ -836,9 +844,14 @@ class Engine:
                 mlp = MLP_LIN_RC if rc else MLP_LIN_SAVED
         else:
             mlp = MLP_FOLD if pre in P["cmlp"] else MLP_CONV
+        # the one-launch MLP backward accumulates all four of fc1 / fc2 weight and bias: one frozen parameter keeps today's launches
+        T = getattr(plan, "trainable", None)
+        mlp_bwd = mlp == MLP_FUSED and self.use_fused_mlp_bwd and Cc == 192 and M >= self.mlp_bwd_min_rows and \
+            (T is None or all(T(pre + n) for n in ("mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")))
         return BlockRoute(x_in, (B, H, W, Cc, ws, shift), pad, attn, wpk, mlp, zscratch=wpk is None and ws * ws > 64,
                           sq_ok=pad is None and plan.dt == torch.bfloat16 and Cc == 192,
-                          wide_ok=plan.dt == torch.bfloat16 and Cc == 192 and attn != ATTN_PADDED and M >= self.wide_linbwd_min_rows)
+                          wide_ok=plan.dt == torch.bfloat16 and Cc == 192 and attn != ATTN_PADDED and M >= self.wide_linbwd_min_rows,
+                          mlp_bwd=mlp_bwd)
 
     def _block_fwd(self, plan, P, tag, blk, x_in, B, H, W):
         ops.set_tag(tag)
@@ -920,7 +933,8 @@ class Engine:
         if r.mlp == MLP_FUSED:
             # fc1 + GELU + fc2 + residual in ONE launch (csrc/mlp.hip): the 4C-wide hidden activation leaves the CU only in training,
             # as GELU(h) for fc2's weight gradient (the backward recomputes h inside the dh GEMM, as below)
-            ha = plan.buf(tag + ".ha", (M, 4 * Cc)) if sm else None
+            # (r.mlp_bwd: the backward recomputes GELU(h) as well - no buffer, the inference form of the launch)
+            ha = plan.buf(tag + ".ha", (M, 4 * Cc)) if sm and not r.mlp_bwd else None
             ops.mlp_fwd(xn2, w[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], w[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"],
                         xm, xo, ha, M, Cc)
         elif r.mlp in (MLP_LIN_RC, MLP_LIN_SAVED):
@@ -997,9 +1011,17 @@ class Engine:
         ln2 = plan.unit(tag + ".attn").runs_bwd or T(pre + "norm2.weight", pre + "norm2.bias")     # d(xn2) and the LayerNorm-2 backward
         fc1 = T(pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
         if r.mlp in (MLP_FUSED, MLP_LIN_RC, MLP_LIN_SAVED):
-            ha = b[tag + ".ha"]
             dh = plan.scratch("dh", (M, 4 * Cc))
-            if r.mlp == MLP_LIN_SAVED:
+            fused = r.mlp_bwd and ops.mlp_bwd(xn2, dY, P["w"][pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], wT[pre + "mlp.fc2.weight"], dh,
+                                              g[pre + "mlp.fc1.weight"], g[pre + "mlp.fc1.bias"], g[pre + "mlp.fc2.weight"],
+                                              g[pre + "mlp.fc2.bias"], M)
+            if r.mlp_bwd and not fused:
+                raise RuntimeError(f"{tag}: sodt_mlp_bwd refused the block its route was recorded for (the forward kept no GELU(h))")
+            ha = None if fused else b[tag + ".ha"]
+            if fused:         # dh, dW1 / db1, dW2 / db2 are done: only dxn = dh fc1.weight is left
+                if ln2:
+                    ops.gemm_nt([SegSpec(dh, 4 * Cc, 0)], wT[pre + "mlp.fc1.weight"], dxn, M, Cc, 4 * Cc)
+            elif r.mlp == MLP_LIN_SAVED:
                 self._linear_bwd(P, pre + "mlp.fc2", dY, ha, dh, M, Cc, 4 * Cc, dgelu_aux=b[tag + ".hp"], plan=plan, need_dx=ln2 or fc1)
             else:       # dh = (dY fc2.weight) * gelu'(xn2 fc1.weight^T + b1): pre-activation recomputed in the first K half
                 if T(pre + "mlp.fc2.weight", pre + "mlp.fc2.bias"):
@@ -1007,7 +1029,8 @@ class Engine:
                 if ln2 or fc1:
                     ops.gemm_nt([SegSpec(xn2), SegSpec(dY)], P["wcat"][pre + "mlp.fc1.weight"], dh, M, 4 * Cc, 2 * Cc,
                                 bias=p[pre + "mlp.fc1.bias"], dgelu_rc=True)
-            self._linear_bwd(P, pre + "mlp.fc1", dh, xn2, dxn, M, 4 * Cc, Cc, plan=plan, need_dx=ln2)
+            if not fused:
+                self._linear_bwd(P, pre + "mlp.fc1", dh, xn2, dxn, M, 4 * Cc, Cc, plan=plan, need_dx=ln2)
         else:
             cp, ca = b[tag + ".cp"], b[tag + ".ca"]
             dc = plan.scratch("dc", (M, Cc))

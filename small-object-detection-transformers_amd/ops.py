@@ -378,6 +378,48 @@ def linear_bwd_wide_splits(M: int) -> int:
     return max(1, min(M // 512, 85))
 
 
+def mlp_bwd(xn: torch.Tensor, dY: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2T: torch.Tensor, dh: torch.Tensor,
+            dW1: torch.Tensor, db1: torch.Tensor, dW2: torch.Tensor, db2: torch.Tensor, M: int, *,
+            hact: Optional[torch.Tensor] = None, ldxn: Optional[int] = None, ldy: Optional[int] = None, lddh: Optional[int] = None,
+            ldha: Optional[int] = None, lddw1: Optional[int] = None, lddw2: Optional[int] = None, splits: Optional[int] = None) -> bool:
+    """Backward of fc2(GELU(fc1(xn))) at C = 192, hidden 768, in ONE launch (plus the slice reduction): dh[M][768] = (dY @ fc2.weight)
+    * gelu'(xn @ w1^T + b1) with the bits of gemm_nt(dgelu_rc=True), dW1 += dh^T xn, db1 += column sums of dh, dW2 += dY^T GELU(h),
+    db2 += column sums of dY; hact (optional) receives the recomputed GELU(h).  w1 is fc1.weight [768][192], w2T the [768][192]
+    operand gemm_nt takes for dY @ fc2.weight.  Eight sibling workgroups per M-slice, one 96-column slab of the hidden dimension
+    each (csrc/mlpbwd.hip).  Returns False, with nothing launched, written or recorded, when sodt_mlp_bwd does not take the layer
+    (SODT_EINVAL): the caller then runs gemm_tn + gemm_nt(dgelu_rc) + gemm_tn."""
+    bf = [xn, dY, w1, w2T, dh] + ([hact] if hact is not None else [])
+    if any(t.dtype != torch.bfloat16 for t in bf) or any(t.dtype != torch.float32 for t in (b1, dW1, db1, dW2, db2)):
+        return False
+    if tuple(w1.shape) != (768, 192) or tuple(w2T.shape) != (768, 192) or b1.numel() != 768 or db1.numel() != 768 or db2.numel() != 192:
+        return False
+    if xn.shape[-1] < 192 or dY.shape[-1] < 192 or dh.shape[-1] < 768 or (hact is not None and hact.shape[-1] < 768):
+        return False
+    sp = mlp_bwd_splits(M) if splits is None else splits
+    part, part_n = None, 0
+    if _tn_scratch is not None and _tn_scratch.device == dY.device and sp > 1:
+        part, part_n = _tn_scratch.data_ptr(), _tn_scratch.numel()
+    fn = _lib.sodt_mlp_bwd
+    args = (xn.data_ptr(), xn.shape[-1] if ldxn is None else ldxn, dY.data_ptr(), dY.shape[-1] if ldy is None else ldy,
+            w1.data_ptr(), w1.stride(0), b1.data_ptr(), w2T.data_ptr(), w2T.stride(0),
+            dh.data_ptr(), dh.shape[-1] if lddh is None else lddh, _p(hact), 0 if hact is None else (hact.shape[-1] if ldha is None else ldha),
+            dW1.data_ptr(), 192 if lddw1 is None else lddw1, db1.data_ptr(), dW2.data_ptr(), 768 if lddw2 is None else lddw2,
+            db2.data_ptr(), M, 192, sp, part, part_n, L.BF16)
+    rc = fn(*args, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc == L.EINVAL:              # refused before any launch
+        return False
+    if rc != 0:
+        raise RuntimeError(f"sodt_mlp_bwd failed with status {rc}")
+    if _active_recorder is not None:
+        _active_recorder.append((fn, args, "sodt_mlp_bwd", _tag))
+    return True
+
+
+def mlp_bwd_splits(M: int) -> int:
+    """M-slices of sodt_mlp_bwd: eight workgroups per slice, 8 x 32 = 256 on 256 CUs, at least 16 stages of 32 rows per slice."""
+    return max(1, min(M // 512, 32))
+
+
 def layernorm_fwd(x, gamma, beta, y, stats, M, Cc):
     _launch("sodt_layernorm_fwd", _p(x), _p(gamma), _p(beta), _p(y), _p(stats), M, Cc, dt_code(x))
 

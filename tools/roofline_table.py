@@ -62,6 +62,14 @@ def cost(name, args):
         # L2 hits.  One partial dW tile per slice written and read, dW itself, the weight once
         return (f"M={g.M} N={g.N} K={g.K} dX+dW wide", g.M * (g.N + 2 * g.K) * ES + (2.0 * g.splits + 2) * g.N * g.K * 4 + g.N * g.K * ES,
                 4.0 * g.M * g.N * g.K)
+    if name == "sodt_mlp_bwd":
+        M, splits = val(args[19]), val(args[21])
+        hact = 1 if args[11] else 0
+        # the single-pass model: xn2 and dY (192 wide) in once, dh (768 wide) out (+ GELU(h) where asked for); seven of the eight
+        # siblings' reads are priced as L2 hits.  One partial tile per slice and weight written and read, both dW, both weight slabs
+        # once; flops: h, dA, dW1, dW2
+        return (f"M={M} C=192 hidden=768 dh+dW1+dW2", M * (2 * 192 + (1 + hact) * 768) * ES + 2 * (2.0 * splits + 2) * 768 * 192 * 4
+                + 2 * 768 * 192 * ES, 8.0 * M * 768 * 192)
     if name in ("sodt_detect_fwd", "sodt_detect_bwd"):
         g = unwrap(args[0])
         M, N = g.B * g.HW, g.na * g.no
