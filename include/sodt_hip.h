@@ -671,6 +671,9 @@ int sodt_prep_weights(const sodt_prep_desc* table_dev, int n, int max_elems, int
  * streaming launch.  All buffers hold n_elems f32 (16-byte aligned, n_elems % 4 == 0); every 4-element chunk belongs to
  * one parameter and group_of_chunk[chunk] (device bytes, nullable = all group 0) picks its hyper-parameters
  * lr / momentum / weight_decay[group] (host arrays of ngroups <= 4); 255 = not trained (cast / EMA only).
+ * Map bytes the call's groups do not name: a byte in [ngroups, 4) is trained with group 0's hyper-parameters (the unused slots
+ * of the 4-entry tables repeat slot 0); every byte from 4 to 254 is what 255 is.  A chunk that is not trained keeps its p and
+ * momentum bits and still gets the EMA and the cast of its unchanged p (unlike sodt_sam_perturb, which writes nothing there).
  *   d = g*grad_scale + wd*p;  m = momentum*m + d;  u = nesterov ? d + momentum*m : m;  p -= lr*u
  *   ema = ema*ema_decay + (1-ema_decay)*p (ema nullable);  p_cast = (cast_dtype) p (p_cast nullable). */
 int sodt_sgd_ema_step(float* p, const float* g, float* mom, float* ema, void* p_cast, int cast_dtype,
@@ -687,7 +690,8 @@ int sodt_sgd_ema_step(float* p, const float* g, float* mom, float* ema, void* p_
  * them in double, as torch forms them from Python floats, and only then rounded to the floats the kernel reads.
  *   coupled: d = g*grad_scale + wd*p, p0 = p;   decoupled: d = g*grad_scale, p0 = p*(1 - lr*wd)
  *   m = b1*m + (1-b1)*d;  v = b2*v + (1-b2)*d*d;  p = p0 - lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
- *   ema, p_cast as in sodt_sgd_ema_step.  SODT_EINVAL: null / misaligned buffers, n_elems % 4, ngroups outside 1..4,
+ *   ema, p_cast and the map bytes ([ngroups, 4): group 0's hyper-parameters; 4..254: as 255, exp_avg and exp_avg_sq kept too)
+ *   as in sodt_sgd_ema_step.  SODT_EINVAL: null / misaligned buffers, n_elems % 4, ngroups outside 1..4,
  *   step < 1, eps <= 0, a beta outside [0, 1), an unknown cast_dtype. */
 int sodt_adam_ema_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* ema, void* p_cast, int cast_dtype,
                        const unsigned char* group_of_chunk, long n_elems, int ngroups, const double* lr,
@@ -717,7 +721,8 @@ typedef struct {
 } sodt_step_ctl;
 
 /* One pass over g (n_elems f32, 16-byte aligned, n_elems % 4 == 0; group_of_chunk as in sodt_sgd_ema_step: chunks marked 255 are
- * not owned and not read); the last block to finish finalises *ctl.  scale and found_inf_in are DEVICE pointers to one f32 each
+ * not owned and never looked at; the entry takes no ngroups: every byte below 4 is owned and every byte from 4 to 254 is what 255
+ * is, exactly the chunks the step entries train); the last block to finish finalises *ctl.  scale and found_inf_in are DEVICE pointers to one f32 each
  * (GradScaler's own tensors), either may be null: scale null = 1, 1 / scale is formed as GradScaler forms it
  * (double reciprocal rounded to f32); found_inf_in is OR-ed into found_inf.  grad_scale is the host factor of the plain
  * entries and composes by multiplication.  max_norm <= 0: no clipping.  SODT_EINVAL: null / misaligned g or ctl (16 bytes),
@@ -730,7 +735,8 @@ int sodt_grad_stats(const float* g, const unsigned char* group_of_chunk, long n_
  * (lr / (1 - beta1^t) and sqrt(1 - beta2^t) are then formed in the kernel, in double from the double hyper-parameters).
  * ctl->skip != 0: p, the momentum / exp_avg / exp_avg_sq are left as they are, while the EMA average and the run-dtype cast
  * still run on the unchanged p (Train.py:450-453 calls ema.update after a skipped step too).  ctl is a DEVICE pointer that a
- * sodt_grad_stats call earlier on the same stream has filled.  SODT_EINVAL additionally: a null or misaligned (16 bytes) ctl. */
+ * sodt_grad_stats call earlier on the same stream has filled.  Map bytes as in the plain entries: below 4 trained ([ngroups, 4)
+ * with group 0's hyper-parameters), 4..254 as 255.  SODT_EINVAL additionally: a null or misaligned (16 bytes) ctl. */
 int sodt_sgd_ema_step_ctl(float* p, const float* g, float* mom, float* ema, void* p_cast, int cast_dtype,
                           const unsigned char* group_of_chunk, long n_elems, int ngroups, const float* lr,
                           const float* momentum, const float* weight_decay, int nesterov, const sodt_step_ctl* ctl,

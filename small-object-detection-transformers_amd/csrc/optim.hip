@@ -14,8 +14,10 @@
 //   p16 = (run dtype) p'                              (skipped when p_cast == NULL)
 //
 // Parameters are padded to multiples of four elements in the flat layout (engine.py), so a 16-byte chunk belongs to one
-// parameter and `group_of_chunk` (one byte per chunk) selects its hyper-parameter group.  HBM-bound: 4 x 4 B read +
-// 3 x 4 B + 2 B written per element.
+// parameter and `group_of_chunk` (one byte per chunk) selects its hyper-parameter group.  A byte below 4 is trained - with slot
+// 0's hyper-parameters when it is not below ngroups, the launchers fill the unused table slots from slot 0 - and every other
+// byte is what 255 is, here and in grad_stats_kernel alike (tests/test_optim_kernels_gpu.py pins both).  HBM-bound: 4 x 4 B
+// read + 3 x 4 B + 2 B written per element.
 //
 // adam_ema_kernel is the sibling for Train.py's --adam (Train.py:147-148: optim.Adam(pg0, lr, betas=(momentum, 0.999)))
 // and for AdamW (basics/optimizer.py:11-33): torch.optim.Adam / AdamW with amsgrad=False, maximize=False, step count t,
