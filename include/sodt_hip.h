@@ -438,6 +438,14 @@ int sodt_bn_silu_bwd_reduce(const void* dy, int lddy, const void* z, const float
 int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, const float* mean_rstd,
                            const float* gamma, const float* beta, const double* red, void* dz,
                            float* dgamma, float* dbeta, long M, int C, int lddz, int dtype, sodt_stream_t st);
+/* pass 2 where the BatchNorm statistics are shared by data-parallel ranks (torch.nn.SyncBatchNorm, Train.py:206-209): the two means
+   of dz are red_global / count_total - the sums of every rank's rows (red_local after its all-reduce) over the rows of all
+   ranks - while dgamma / dbeta += (float)red_local, this rank's own sums: the gradient all-reduce combines those like every other
+   gradient.  red_global == red_local and count_total == M give sodt_bn_silu_bwd_apply bit for bit.  count_total >= M. */
+int sodt_bn_silu_bwd_apply_sync(const void* dy, int lddy, const void* z, const float* mean_rstd,
+                                const float* gamma, const float* beta, const double* red_local,
+                                const double* red_global, long count_total, void* dz, float* dgamma, float* dbeta,
+                                long M, int C, int lddz, int dtype, sodt_stream_t st);
 
 /* dst[(b,y,x)][coff : coff+C] = src[(b, y>>shr, x>>shr)][0:C]  (nn.Upsample nearest + Concat slot) */
 int sodt_copy_rows(const void* src, int lds_, void* dst, int ldd, int B, int Ho, int Wo, int shr, int C,

@@ -184,6 +184,7 @@ SIGNATURES = {
     "sodt_bn_silu_fwd": [_P, _P, _P, _P, _P, _I, _L, _I, _I, _P],
     "sodt_bn_silu_bwd_reduce": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _I, _P],
     "sodt_bn_silu_bwd_apply": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
+    "sodt_bn_silu_bwd_apply_sync": [_P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _I, _I, _I, _P],
     "sodt_copy_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_gather_sum_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sodt_detect_unpermute": [_P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -222,19 +222,29 @@ __device__ __forceinline__ float bn_dz(float d, float xh, float a, float gars, f
 
 // dz = gamma rstd (g - mean_m g - xhat mean_m (g xhat)) from the finished sums; workgroup 0 also adds them to dgamma / dbeta.
 // The two means are one f64 product rounded once to f32, formed once per thread.
-template <typename T>
+// SYNC (sodt_bn_silu_bwd_apply_sync, BatchNorm statistics shared by data-parallel ranks): the means are those of the rows of every
+// rank, red.all / red.count - the sums after their all-reduce and the total row count - while dgamma / dbeta still take this rank's
+// own sums red.local (the gradient all-reduce adds the ranks' up like any other gradient).  The type of `red` follows the flag:
+// the pointer it always was, or the record of that instantiation alone - so the other's kernel arguments, hidden ones included,
+// lie where they always did and it compiles to the same instructions, byte for byte.
+template <bool SYNC> struct BnSums { typedef const double* __restrict__ type; };
+template <> struct BnSums<true> { struct type { const double* local; const double* all; long count; }; };
+
+template <typename T, bool SYNC>
 __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z,
                                                                const float* __restrict__ mr, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, const double* __restrict__ red,
+                                                               const float* __restrict__ beta, typename BnSums<SYNC>::type red,
                                                                T* __restrict__ dz, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta, long M, int C, int lddz) {
   constexpr int KPL = TT<T>::KPL;
   constexpr int U = BN_APP_ROWS;
   const int CH = C / KPL;
   const int rpp = 256 / CH;                  // rows per pass
-  const double invM = 1.0 / (double)M;
+  const double* rloc; const double* rsum; long rows;
+  if constexpr (SYNC) { rloc = red.local; rsum = red.all; rows = red.count; } else { rloc = red; rsum = red; rows = M; }
+  const double invM = 1.0 / (double)rows;
   if (blockIdx.x == 0) {
-    for (int c = threadIdx.x; c < C; c += 256) { dbeta[c] += (float)red[c]; dgamma[c] += (float)red[C + c]; }
+    for (int c = threadIdx.x; c < C; c += 256) { dbeta[c] += (float)rloc[c]; dgamma[c] += (float)rloc[C + c]; }
   }
   const int rl = threadIdx.x / CH, ch = threadIdx.x - rl * CH;
   if (rl >= rpp) return;
@@ -244,7 +254,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_apply_kernel(const T* __restr
   for (int j = 0; j < KPL; ++j) {
     const int c = c0 + j;
     mu[j] = mr[c]; rs[j] = mr[C + c]; ga[j] = gamma[c]; be[j] = beta[c]; gr[j] = ga[j] * rs[j];
-    mg[j] = (float)(red[c] * invM); mgx[j] = (float)(red[C + c] * invM);
+    mg[j] = (float)(rsum[c] * invM); mgx[j] = (float)(rsum[C + c] * invM);
   }
   const long stride = (long)gridDim.x * rpp;
   for (long m = (long)blockIdx.x * rpp + rl; m < M; m += U * stride) {
@@ -500,8 +510,23 @@ extern "C" int sodt_bn_silu_bwd_apply(const void* dy, int lddy, const void* z, c
   if (!dy || !z || !red || !dz || !dgamma || !dbeta || M <= 0 || C <= 0 || (C % kpl) || (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
   if (lddz < C || (lddz % kpl)) return SODT_EINVAL;
   const unsigned gr = bn_grid(M, C / kpl, BN_APP_ROWS, BN_APP_GRID);
-  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C, lddz);
-  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C, lddz);
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16, false>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, red, (bf16*)dz, dgamma, dbeta, M, C, lddz);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float, false>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, red, (float*)dz, dgamma, dbeta, M, C, lddz);
+  return SODT_EINVAL;
+}
+
+extern "C" int sodt_bn_silu_bwd_apply_sync(const void* dy, int lddy, const void* z, const float* mean_rstd,
+                                           const float* gamma, const float* beta, const double* red_local,
+                                           const double* red_global, long count_total, void* dz, float* dgamma, float* dbeta,
+                                           long M, int C, int lddz, int dtype, sodt_stream_t st) {
+  const int kpl = dtype == SODT_BF16 ? 8 : 4;
+  if (!dy || !z || !red_local || !red_global || !dz || !dgamma || !dbeta || M <= 0 || count_total < M || C <= 0 || (C % kpl) ||
+      (lddy % kpl) || C / kpl > 256) return SODT_EINVAL;
+  if (lddz < C || (lddz % kpl)) return SODT_EINVAL;
+  const unsigned gr = bn_grid(M, C / kpl, BN_APP_ROWS, BN_APP_GRID);
+  const BnSums<true>::type sums{red_local, red_global, count_total};
+  if (dtype == SODT_BF16) return sodt_launch<bn_silu_bwd_apply_kernel<bf16, true>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const bf16*)dy, lddy, (const bf16*)z, mean_rstd, gamma, beta, sums, (bf16*)dz, dgamma, dbeta, M, C, lddz);
+  if (dtype == SODT_F32) return sodt_launch<bn_silu_bwd_apply_kernel<float, true>>(dim3(gr), dim3(256), 0, (hipStream_t)st, (const float*)dy, lddy, (const float*)z, mean_rstd, gamma, beta, sums, (float*)dz, dgamma, dbeta, M, C, lddz);
   return SODT_EINVAL;
 }
 

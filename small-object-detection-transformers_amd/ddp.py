@@ -29,6 +29,11 @@ Two ways to stay correct, both covered by tests/test_ddp_*.py:
     next backward adds to it (SUM mode; MEAN mode needs no correction), so reducing on every
     micro-step - what the reference's DDP does - gives the same sums.
 
+``--sync-bn`` (Train.py:206-209): ``convert_sync_batchnorm(model)`` makes the head's BatchNorms
+take their training-mode statistics over every rank's rows; the engine exchanges the f64
+sums through ``GradReducer.all_reduce_stats`` around ``sodt_bn_finalize`` and
+``sodt_bn_silu_bwd_apply_sync``.
+
 torch.distributed's "nccl" backend IS RCCL on ROCm; the tests drive the same code with gloo.
 """
 from __future__ import annotations
@@ -102,6 +107,44 @@ class GradReducer:
                 part.mul_(1.0 / self.world)
         self._pending = []
         self._dirty = True
+
+    def all_reduce_stats(self, t: torch.Tensor) -> None:
+        """Blocking SUM of a BatchNorm statistics buffer (f64) over the group, in place: the one collective call site of
+        synchronised BatchNorm (convert_sync_batchnorm), twice per head Conv and step.  no_sync() does not reach it: as in
+        torch, it holds back the gradient exchange only.  One rank: nothing to add."""
+        if self.world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+
+    def gather_shapes(self, B: int, H: int, W: int):
+        """[(B, H, W) of every rank], one all_gather: synchronised BatchNorm weighs every rank's sums alike, so the engine
+        compares the per-rank batches once per new plan, before the first statistics collective of that plan."""
+        cpu = dist.get_backend(self.group) == "gloo"
+        mine = torch.tensor([B, H, W], dtype=torch.int64, device="cpu" if cpu else torch.device("cuda", torch.cuda.current_device()))
+        out = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(out, mine, group=self.group)
+        return [tuple(int(v) for v in o.tolist()) for o in out]
+
+
+def sync_bn_in_force(flag, reducer) -> bool:
+    """The engine's gate for synchronised BatchNorm: the model's flag AND a reducer of more than one rank.  Otherwise - one rank,
+    no reducer - every launch list is what it is without the flag and no statistics collective is issued."""
+    return bool(flag) and reducer is not None and reducer.world > 1
+
+
+def convert_sync_batchnorm(model, group=None):
+    """In place of ``torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` (Train.py:206-209): the head's BatchNorms take their
+    training-mode statistics over the rows of every rank of the attached reducer's group, forward and backward, and every
+    rank ends a step with the same running statistics.  The engine never calls a BatchNorm module, so no module is replaced:
+    every ``nn.BatchNorm2d`` stays what it is (state_dict keys, the ``type(mod) is nn.BatchNorm2d`` initialisation and the EMA
+    copy depend on that) and the model carries the flag ``sync_bn``, read at every forward.  It takes effect once a reducer
+    of more than one rank is attached (``attach``, before or after this call); eval mode, one rank and a model without a
+    reducer run as they always did.  Every rank must run the same per-rank batch shape.  ``group`` is accepted for the
+    signature's sake and must be the reducer's group: the statistics travel on that one."""
+    red = getattr(model, "grad_reducer", None)
+    if group is not None and red is not None and red.group is not group:
+        raise ValueError("convert_sync_batchnorm: the statistics are exchanged on the attached reducer's group; pass that group or None")
+    model.sync_bn = True
+    return model
 
 
 def attach(model, group=None, average: bool = True, broadcast: bool = True):

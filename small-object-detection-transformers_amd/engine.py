@@ -24,6 +24,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import freeze
+from .ddp import sync_bn_in_force
 from .headgraph import Ref, parse_head
 from .ops import TAPS3, SegSpec
 
@@ -67,6 +68,9 @@ class Plan:
         self.enc_gin: Optional[list] = None       # [(buf, ld, off, c)]: where the head leaves d(f0), d(f1), d(f2)
         self.det_fused: Optional[bool] = None     # Detect's backward is the live one-pass launch, not part of bwd_main (set with bwd_main)
         self.bn_marks: List[list] = []            # [index in fwd_main, BatchNorm2d, its name, momentum recorded] of every sodt_bn_finalize
+        # synchronised BatchNorm (Engine.sync_bn with more than one rank; empty otherwise): where a replay stops for a collective
+        self.sbn_fwd: List[Tuple[int, torch.Tensor]] = []                 # (a bn_marks index, the conv's stats) - all-reduced in place
+        self.sbn_bwd: List[Tuple[int, torch.Tensor, torch.Tensor]] = []   # (index in bwd_main of the apply launch, red, red_all)
 
     def unit(self, name):
         """the freeze.UnitRecord of unit `name`"""
@@ -278,6 +282,11 @@ class Engine:
         # Shifted blocks on a grid that is no multiple of their window (S % 64 == 32: stage 2) run csrc/attention_sp.hip instead of
         # being refused.  Opt-in; run() copies Model.pad_shifted_blocks here and drops the cached plans when it changes.
         self.pad_shifted_blocks = False
+        # torch.nn.SyncBatchNorm's semantics for the head's BatchNorms (ddp.convert_sync_batchnorm): run() copies Model.sync_bn here
+        # and drops the cached plans when it - or whether it is in force - changes.  In force (_sbn_on) only with a reducer of more
+        # than one rank: otherwise every launch list is what it is without the flag.
+        self.sync_bn = False
+        self._sbn_on = False
         self.use_fused_wmsa = True     # tests / tools may switch the fused block kernel off to compare with the four launches it replaces
         self.use_fused_mlp = True      # the same for the fused linear MLP (csrc/mlp.hip) against its two GEMM launches
         # bf16, C = 192: backward of attn.proj and of the conv-MLP's fc2 as ONE launch each (csrc/linbwd.hip: dX and dW from one read
@@ -566,6 +575,11 @@ class Engine:
         if psb != self.pad_shifted_blocks:
             self.pad_shifted_blocks = psb
             self.plans.clear()                                   # recorded launch lists hold the routes of the other setting
+        sbn = bool(getattr(self.model, "sync_bn", False))
+        sbn_on = sync_bn_in_force(sbn, self.ddp)
+        if sbn != self.sync_bn or sbn_on != self._sbn_on:
+            self.sync_bn, self._sbn_on = sbn, sbn_on
+            self.plans.clear()                                   # the launch lists of the other setting stop elsewhere, for other collectives
         # a training plan belongs to one set of requires_grad flags (its launch lists and its workspace follow them), read here at
         # every forward: freezing at an epoch boundary (Train.py:328-333) needs no call.  Eval plans save nothing and have no
         # backward: one plan whatever the flags (an EMA copy is frozen throughout).
@@ -575,6 +589,8 @@ class Engine:
         if plan is None:
             while len(self.plans) >= self.MAX_PLANS:
                 self.plans.pop(next(iter(self.plans)))          # dicts keep insertion order: the first key is the LRU one
+            if training and self._sbn_on:
+                self._check_rank_shapes(B, H, W)
             plan = Plan(B, S, dt, training, self.dev, fz)
         self.plans[key] = plan                                   # (re)insert as most recently used
         out_sr = None
@@ -587,6 +603,24 @@ class Engine:
             if self.sr and training:                              # model.py:284-287: the branch runs in training mode only
                 out_sr = self._sr_forward(plan)
         return pred, self._features(plan), out_sr
+
+    def _check_rank_shapes(self, B, H, W):
+        """Synchronised BatchNorm counts M * world rows and gives every rank's sums the same weight: every rank must run the same
+        per-rank batch.  One all_gather per new training plan, so a mismatch raises on every rank, before any statistics
+        collective of the plan (a rank that stopped alone would leave the others waiting in theirs)."""
+        shapes = self.ddp.gather_shapes(B, H, W)
+        if any(s != shapes[0] for s in shapes):
+            raise RuntimeError(f"sync_bn: the ranks run different per-rank batches (B, H, W) = {shapes}: synchronised BatchNorm "
+                               "needs the same batch size and image size on every rank (uneven batches are not built)")
+
+    def _sbn_fwd_collective(self, stats):
+        """the conv's f64 column sums [SODT_STATS_REPL][2][C] (one contiguous slice of zero pool "f") become those of every rank"""
+        self.ddp.all_reduce_stats(stats)
+
+    def _sbn_bwd_collective(self, red, red_all):
+        """red_all = sum over the ranks of red, the BN-backward sums [2][C] f64; red stays this rank's own (dgamma / dbeta)"""
+        red_all.copy_(red)
+        self.ddp.all_reduce_stats(red_all)
 
     def decode(self, pred):
         B, na, ny, nx, no = pred.shape
@@ -663,7 +697,17 @@ class Engine:
             plan.fwd_main = rec.calls
         else:
             self._sync_bn_momentum(plan)
-            self._replay(plan, "fwd_main", plan.fwd_main, self.probes_fwd)
+            if plan.sbn_fwd:
+                # synchronised BatchNorm: replay in segments that end in front of every sodt_bn_finalize, whose statistics are
+                # all-reduced there (the recording issued the same collectives inline, in the same order)
+                pos = 0
+                for idx, stats in plan.sbn_fwd:
+                    ops.replay(plan.fwd_main, probes=self.probes_fwd, start=pos, end=idx)
+                    self._sbn_fwd_collective(stats)
+                    pos = idx
+                ops.replay(plan.fwd_main, probes=self.probes_fwd, start=pos)
+            else:
+                self._replay(plan, "fwd_main", plan.fwd_main, self.probes_fwd)
         # (4) Detect: live (fresh output tensor every call)
         pred = torch.empty(B, self.na, th, tw, self.no, device=self.dev, dtype=torch.float32)
         hrow, hc = self.head.head_out
@@ -1198,7 +1242,16 @@ class Engine:
             at = ops.recorded_count()
             if at is not None:
                 plan.bn_marks.append([at, bn, pname + "bn", mom])
-            ops.bn_finalize(stats, mr, bufs[pname + "bn.running_mean"], bufs[pname + "bn.running_var"], M, Cout, 1e-3, mom)
+            count = M
+            if self._sbn_on:
+                # the statistics of every rank's rows: the sums are all-reduced between the launch that formed them and
+                # sodt_bn_finalize, which divides by the total count (unbiased running variance included).  Issued here while
+                # recording; a replay stops at this index for it (_forward).  A frozen unit's statistics are shared too.
+                if at is not None:
+                    plan.sbn_fwd.append((at, stats))
+                self._sbn_fwd_collective(stats)
+                count = M * self.ddp.world
+            ops.bn_finalize(stats, mr, bufs[pname + "bn.running_mean"], bufs[pname + "bn.running_var"], count, Cout, 1e-3, mom)
             ops.bn_silu_fwd(z, mr, p[pname + "bn.weight"], p[pname + "bn.bias"], y, ldy, M, Cout)
         else:
             mr = plan.buf(tag + ".mr", (2, Cout), torch.float32)
@@ -1228,8 +1281,20 @@ class Engine:
         dz, lddz, dz_off = dz_out if dz_out is not None else (plan.buf(tag + ".dz", (M, Cout)), Cout, 0)
         ops.bn_silu_bwd_reduce(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, M, Cout,
                                dy_off=dy_off)
-        ops.bn_silu_bwd_apply(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, dz,
-                              g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off, lddz=lddz, dz_off=dz_off)
+        if self._sbn_on:
+            # the two means of dz run over every rank's rows: a copy of the sums is all-reduced (here while recording; a replay
+            # stops at this index for it, _backward), dgamma / dbeta keep this rank's own sums for the gradient all-reduce
+            red_all = plan.zbuf("b", tag + ".red_all", (2, Cout), torch.float64)
+            at = ops.recorded_count()
+            if at is not None:
+                plan.sbn_bwd.append((at, red, red_all))
+            self._sbn_bwd_collective(red, red_all)
+            ops.bn_silu_bwd_apply_sync(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red,
+                                       red_all, M * self.ddp.world, dz, g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout,
+                                       dy_off=dy_off, lddz=lddz, dz_off=dz_off)
+        else:
+            ops.bn_silu_bwd_apply(dy, lddy, b[tag + ".z"], b[tag + ".mr"], p[pname + "bn.weight"], p[pname + "bn.bias"], red, dz,
+                                  g[pname + "bn.weight"], g[pname + "bn.bias"], M, Cout, dy_off=dy_off, lddz=lddz, dz_off=dz_off)
         cin = K // (k * k)
         if not plan.trainable(pname + "conv.weight"):
             pass
@@ -1457,13 +1522,21 @@ class Engine:
             with ops.Recorder() as rec:
                 self._backward_main(plan, P)
             plan.bwd_main = rec.calls
-        elif self.ddp is not None and self.ddp.world > 1 and self.ddp.sync and plan.bwd_marks:
-            # replay in segments: at every mark one more bucket of the flat buffer is final and its all-reduce starts
-            overlap = True
+        elif self.ddp is not None and self.ddp.world > 1 and ((self.ddp.sync and plan.bwd_marks) or plan.sbn_bwd):
+            # replay in segments: at every mark one more bucket of the flat buffer is final and its all-reduce starts; with
+            # synchronised BatchNorm the list also stops in front of every sodt_bn_silu_bwd_apply_sync for the sums of the other
+            # ranks (no_sync() holds back the buckets, never those).  Both lists are in index order; merged, the buckets start
+            # where they always did.
+            overlap = bool(self.ddp.sync and plan.bwd_marks)
+            stops = [(idx, 1, (lo, hi)) for idx, lo, hi in plan.bwd_marks] if overlap else []
+            stops += [(idx, 0, (red, red_all)) for idx, red, red_all in plan.sbn_bwd]
             pos = 0
-            for idx, lo, hi in plan.bwd_marks:
+            for idx, bucket, what in sorted(stops, key=lambda s_: s_[:2]):
                 ops.replay(plan.bwd_main, probes=self.probes_bwd, start=pos, end=idx)
-                self.ddp.reduce_async(self.flat_grad[lo:hi])
+                if bucket:
+                    self.ddp.reduce_async(self.flat_grad[what[0]:what[1]])
+                else:
+                    self._sbn_bwd_collective(*what)
                 pos = idx
             ops.replay(plan.bwd_main, probes=self.probes_bwd, start=pos)
         else:

@@ -388,6 +388,9 @@ class Model(nn.Module):
         # True: shifted blocks whose grid is no multiple of their 8-token window run on the reference's zero padding
         # (csrc/attention_sp.hip) instead of being refused - every multiple of 32 from 576 runs, and 544.  Read at each forward.
         self.pad_shifted_blocks = False
+        # True (ddp.convert_sync_batchnorm, Train.py:206-209): with a reducer of more than one rank attached, the head's BatchNorms
+        # take their training-mode statistics over every rank's rows.  Read at each forward.
+        self.sync_bn = False
         # the passes of forward(augment=True) (model.py:157-158): scales in (0, 1], flips None / 2 (up-down) / 3 (left-right),
         # equal length, at most four.  Read and validated at each augmented forward (tta.check_passes).
         self.tta_scales = (1, 0.83, 0.67)

@@ -623,6 +623,15 @@ def bn_silu_bwd_apply(dy, lddy, z, mean_rstd, gamma, beta, red, dz, dgamma, dbet
             Cc if lddz is None else lddz, dt_code(z))
 
 
+def bn_silu_bwd_apply_sync(dy, lddy, z, mean_rstd, gamma, beta, red_local, red_global, count_total, dz, dgamma, dbeta, M, Cc,
+                           dy_off=0, lddz=None, dz_off=0):
+    """bn_silu_bwd_apply with the statistics of every data-parallel rank: the means of dz are red_global / count_total (the
+    all-reduced sums over the rows of all ranks), dgamma / dbeta take this rank's red_local."""
+    _launch("sodt_bn_silu_bwd_apply_sync", dy.data_ptr() + dy_off * dy.element_size(), lddy, _p(z), _p(mean_rstd), _p(gamma),
+            _p(beta), _p(red_local), _p(red_global), count_total, dz.data_ptr() + dz_off * dz.element_size(), _p(dgamma),
+            _p(dbeta), M, Cc, Cc if lddz is None else lddz, dt_code(z))
+
+
 def copy_rows(src, lds, dst, ldd, B, Ho, Wo, shr, Cc, dst_off=0):
     _launch("sodt_copy_rows", _p(src), lds, dst.data_ptr() + dst_off * dst.element_size(), ldd, B, Ho, Wo, shr, Cc, dt_code(src))
 
